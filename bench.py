@@ -17,14 +17,19 @@ stripes travel to rank f % N (blinky_amd.multigpu.exchange_rotating), overlapped
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-launches itself under
 `python -m torch.distributed.run --nproc-per-node N`; a world size that differs from --gpus is an error.
 
-The timed region of K steps is repeated (--repeats; by default as many regions as it takes to keep the GPU busy for
---min-gpu-seconds, at least 31; each bracketed by barrier + synchronize, max over ranks); `value` is the MEDIAN region,
-min / max are printed beside it.  `value_one_stream` is the same measurement with every launch on one stream - the figure
-`roofline.kernel_ms_per_launch` (the kernel alone, HIP events) must be consistent with.
-At N = 1 the line also carries `configs_extra` (BASELINE.json configs[1], 1920x1080 cube/stereographic, timed the same
-way), `predicted_stripe_complete` (rank r's stripe for N = 2 / 4 / 8 timed on this GPU, max over ranks) and `build_ms` - the
-metric's other half: bk_build at the headline's size as a call, for its own lens, quincuncial and two forward-map lenses.
-Prints ONE JSON line (rank 0).  `value` = whole-job Mpixels/s = W*H*frames*steps / time.
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up with W steps (continued until the warm-up has lasted
+WARMUP_MIN_S), times ONE region of exactly K steps (bracketed by barrier + synchronize, max over ranks), writes the last
+step's frames if --dump-outputs is given, and prints ONE JSON line (rank 0): `value` = whole-job Mpixels/s =
+W*H*frames*K / time of the region, `ms_per_step` = that time / K.
+Everything else it measures or checks is behind --full, which times the same region first and then goes on:
+the region repeated (--repeats; by default as many regions as it takes to keep the GPU busy for --min-gpu-seconds, at least
+31; median / min / max in `timed_regions`), `value_one_stream` - the same measurement with every launch on one stream, the
+figure `roofline.kernel_ms_per_launch` (the kernel alone, HIP events) must be consistent with - the roofline, the resident
+apply, the HBM traffic (rocprofv3 child runs) and, at N = 1, `configs_extra` (BASELINE.json configs[1], 1920x1080
+cube/stereographic, timed the same way, and more), `predicted_stripe_complete` (rank r's stripe for N = 2 / 4 / 8 timed on
+this GPU, max over ranks), `build_ms` - the metric's other half: bk_build at the headline's size as a call, for its own lens,
+quincuncial and two forward-map lenses - and the CPU baseline; at N > 1 the first step's frames checked against a full-frame
+warp and the one-GPU scaling reference.  --full also writes the whole record to bench_detail.json.
 """
 import argparse
 import hashlib
@@ -46,6 +51,7 @@ ALGO_BYTES_PER_PX = 6          # 4 B lensmap index + 1 B texel + 1 B store (SURV
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s
 DEFAULT_FRAMES = 64            # frames per step at every --gpus N (one workload for the whole scaling curve)
 EXTRA_FRAMES = 16              # configs_extra / value_at_16_frames: the 16-frame launches rounds 1-4 reported
+WARMUP_MIN_S = 0.2            # the warm-up lasts at least this long (main: a short region right after setup runs slow)
 KERNEL_SOURCES = ("blinky_amd/csrc/bk_apply_coop.hip", "blinky_amd/csrc/bk_apply.hip", "blinky_amd/csrc/bk_build_params.h")
 
 
@@ -461,19 +467,20 @@ def compact_line(out):
     record (configs_extra, predicted stripes, timed regions, the traffic model, every prose note) goes to bench_detail.json."""
     def pick(d, keys):
         return {k: d[k] for k in keys if isinstance(d, dict) and k in d}
-    rf, cfg = out["roofline"], out["config"]
-    sf = rf.get("single_frame") or {}
-    res = sf.get("resident") if isinstance(sf.get("resident"), dict) else {}
     line = pick(out, ("metric", "value", "value_one_stream", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "ms_per_step_one_stream",
                       "higher_is_better", "scaling", "vs_baseline", "dtype", "data"))
-    line["config"] = pick(cfg, ("workload", "frames_per_step", "ring_globes", "parallelism", "streams"))
-    line["roofline"] = pick(rf, ("bound", "achieved", "peak", "unit", "frac", "traffic", "frac_traffic", "frac_compulsory", "kernel_ms_per_launch",
-                                 "kernel_ms_min", "kernel_ms_max"))
-    line["roofline"]["single_frame_us"] = sf.get("us")
-    line["roofline"]["resident_us"] = res.get("us")
-    line["roofline"]["resident_submit_wait_host_us"] = res.get("one_at_a_time_host_us")
-    line["roofline"]["frac_note"] = ("frac = the contract's 6 B/px / kernel time / peak; the kernel reads a 2-byte address once per 8 frames instead of "
-                                     "a 4-byte index per pixel and frame, so frac > 1 is not utilisation: frac_traffic (PMC bytes) is")
+    line["config"] = pick(out["config"], ("workload", "frames_per_step", "ring_globes", "parallelism", "streams"))
+    if "roofline" in out:                             # (--full)
+        rf = out["roofline"]
+        sf = rf.get("single_frame") or {}
+        res = sf.get("resident") if isinstance(sf.get("resident"), dict) else {}
+        line["roofline"] = pick(rf, ("bound", "achieved", "peak", "unit", "frac", "traffic", "frac_traffic", "frac_compulsory", "kernel_ms_per_launch",
+                                     "kernel_ms_min", "kernel_ms_max"))
+        line["roofline"]["single_frame_us"] = sf.get("us")
+        line["roofline"]["resident_us"] = res.get("us")
+        line["roofline"]["resident_submit_wait_host_us"] = res.get("one_at_a_time_host_us")
+        line["roofline"]["frac_note"] = ("frac = the contract's 6 B/px / kernel time / peak; the kernel reads a 2-byte address once per 8 frames instead of "
+                                         "a 4-byte index per pixel and frame, so frac > 1 is not utilisation: frac_traffic (PMC bytes) is")
     if "cpu_baseline" in out:
         cb = out["cpu_baseline"]
         line["cpu_baseline"] = pick(cb, ("value", "unit", "cores", "kind", "build_ms"))
@@ -495,14 +502,41 @@ def compact_line(out):
                                                                                ((c.get("single_frame") or {}).get("resident") or {}).get("us")]
                                                                               if "error" not in c else "error") for c in extras}
         line["extras_are"] = "[kernel us/launch, frac_traffic, resident us/frame]"
-    line["detail"] = out.get("detail_file")
+    if "detail_file" in out:
+        line["detail"] = out["detail_file"]
     text = json.dumps(line, separators=(",", ":"))
     if len(text) > COMPACT_LIMIT:                     # never let an optional key cost the headline
         for k in ("extras", "extras_are", "stripes", "exchange"):
             line.pop(k, None)
-        line["roofline"].pop("frac_note", None)
+        line.get("roofline", {}).pop("frac_note", None)
         text = json.dumps(line, separators=(",", ":"))
     return text
+
+
+DUMP_SAMPLE = 1 << 21         # pixels of the last step's frames in the sample --dump-outputs writes
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, frames):
+    """--dump-outputs: what the timed path computed in its last step - that batch launch's frames (uint8 [F, H, W], on the device) -
+    as float32 .npy files in `path`, 58 MB at the headline's size (at most 64 MB): the batch's first frame whole (every pixel the
+    lensmap maps), and one pixel drawn from each of DUMP_SAMPLE runs of equal length (to a pixel) of the frames laid end to end
+    by a generator with a fixed seed, so that runs with the same arguments sample the same places; those places (flat indices,
+    float64) beside it."""
+    import numpy as np
+    import torch
+    flat = frames.reshape(-1)
+    n = flat.numel()
+    k = min(DUMP_SAMPLE, n)
+    edges = np.arange(k + 1, dtype=np.int64) * n // k
+    idx = edges[:-1] + (np.random.default_rng(DUMP_SEED).random(k) * np.diff(edges)).astype(np.int64)
+    arrays = {"last_step_frame0": frames[0].float().cpu().numpy(),
+              "last_step_sample": flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy(),
+              "last_step_sample_index": idx.astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def emit(out, detail_path):
@@ -539,21 +573,27 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=5, help=f"warm-up steps before the timed ones (continued until the warm-up has lasted {WARMUP_MIN_S} s)")
     ap.add_argument("--frames", type=int, default=0,
                     help="frames per step (batch warped by one launch); default 64 for EVERY --gpus N, so that the driver's 1/2/4/8 curve divides "
                          "like by like (rounds 1-4 ran 16 at N = 1: `value_at_16_frames` keeps that figure); a 270-row stripe of 16 frames is a "
                          "~10 us launch against a ~5.5 us back-to-back launch floor (launch-bound, not bandwidth-bound)")
     ap.add_argument("--no-rebalance", action="store_true", help="N > 1: keep stripes of equal height instead of stripes of equal block-map cost")
     ap.add_argument("--ring", type=int, default=64, help="distinct resident globes the steps cycle through")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's K timed steps, everything else this benchmark measures and checks (see the module docstring); "
+                         "the full record goes to --detail")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the frames the last step computed (the batch's first frame whole and a fixed, "
+                         "seeded sample of every frame's pixels) as float32 .npy files into DIR (--gpus 1)")
     ap.add_argument("--repeats", type=int, default=0,
-                    help="how many times the K-step timed region is measured (median reported); 0 = as many as keep the GPU busy "
-                         "for --min-gpu-seconds, at least 31")
+                    help="--full: how many times the K-step timed region is measured (timed_regions: median / min / max); 0 = as many as "
+                         "keep the GPU busy for --min-gpu-seconds, at least 31")
     ap.add_argument("--min-gpu-seconds", type=float, default=3.0,
-                    help="with --repeats 0: total GPU-timed seconds the regions should add up to (a 50-step region is ~3 ms)")
-    ap.add_argument("--no-extra", action="store_true", help="skip configs_extra (1080p C2) and predicted_stripe_complete")
+                    help="--full, with --repeats 0: total GPU-timed seconds the regions should add up to (a 50-step region is ~3 ms)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip configs_extra (1080p C2) and predicted_stripe_complete")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not measure roofline.traffic live (two child runs under rocprofv3 --pmc); use the stamped record in profiles/ if it matches")
+                    help="--full: do not measure roofline.traffic live (two child runs under rocprofv3 --pmc); use the stamped record in profiles/ if it matches")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child-config", default="", help=argparse.SUPPRESS)
     ap.add_argument("--shape", type=int, default=0, help=argparse.SUPPRESS)
@@ -561,15 +601,17 @@ def main():
                     help="HIP streams the steps alternate between: the tail of a batch launch (its last, partly filled round of "
                          "workgroups) then overlaps the ramp of the next; 1 = every launch on one stream")
     ap.add_argument("--variant", type=int, default=-1, help="apply kernel variant (-1 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--detail", default="", help="where the full record goes (default: bench_detail.json beside bench.py); stdout's last line is the compact one")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--detail", default="", help="--full: where the full record goes (default: bench_detail.json beside bench.py); stdout's last line is the compact one")
     ap.add_argument("--check", action="store_true",
                     help="after the timed region, compare the FNV-1a-64 of every frame this rank holds with the reference's golden frames "
                          "(tests/golden/lensmaps.json, recorded from the unmodified fisheye.c)")
     ap.add_argument("--no-first-step-check", action="store_true",
-                    help="N > 1: skip the check of the first step's reassembled frames against a full-frame warp (on by default: the first "
+                    help="--full, N > 1: skip the check of the first step's reassembled frames against a full-frame warp (on by default: the first "
                          "time the exchange runs on a node is the time to find out)")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes the frames of one GPU's batch launch: use it with --gpus 1")
     if args.traffic_child:
         if args.frames <= 0:
             args.frames = DEFAULT_FRAMES
@@ -810,18 +852,22 @@ def main():
             exchange_mode = "root"
     run_step = step if exchange_mode == "rotating" else step_root
 
+    last_step = -1
+
     def timed_region(first):
         """EXACTLY K steps between barrier + synchronize on both sides; max over ranks"""
+        nonlocal last_step
         barrier()
         t0 = time.perf_counter()
         for i in range(first, first + args.steps):
             run_step(i)
         drain()
         barrier()
+        last_step = first + args.steps - 1
         return max_over_ranks(time.perf_counter() - t0)
 
     first_step_check = None
-    if world > 1 and not args.no_first_step_check and exchange_mode == "rotating":
+    if args.full and world > 1 and not args.no_first_step_check and exchange_mode == "rotating":
         # step 0 for real, then every frame this rank ends up holding against the same frame warped whole here; every rank's
         # verdict (and its error text) travels to rank 0 and into the JSON line
         msg = "ok"
@@ -860,17 +906,100 @@ def main():
                 print(json.dumps({"metric": "warped Mpixels/s (lensmap apply)", "value": None, "n_gpus": world, "error": "first-step check failed",
                                   "first_step_check": first_step_check}))
             sys.exit(3)
+
+    def finish():
+        if comm:
+            comm.synchronize()
+            comm.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    # warm-up: the --warmup steps, then more (doubling blocks, the same on every rank) until the steps have kept the GPU busy for
+    # WARMUP_MIN_S - right after setup a 50-step region runs ~3 % slow (4K panini x64, one process: 2.56 Tpx/s after 5 warm-up steps,
+    # 2.64 after 0.1 s of them; 500-step regions 0.4 %, 2000-step regions not measurably).  The timed region starts at step
+    # --warmup whatever the count, so it warps the same globes every run.
+    barrier()
+    t0 = time.perf_counter()
     for i in range(args.warmup):
         run_step(i)
     drain()
+    barrier()
+    block = 8
+    while max_over_ranks(time.perf_counter() - t0) < WARMUP_MIN_S:
+        for i in range(block):
+            run_step(i)
+        drain()
+        barrier()
+        block *= 2
+    # the headline: ONE region of exactly --steps steps
+    regions = [timed_region(args.warmup)]
+    elapsed = regions[0]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, stripes[last_step % NB])
+
+    if args.check:
+        # Every frame this rank ends up holding after the LAST step of the timed region, against the reference: FNV-1a-64 per frame
+        # compared with tests/golden/lensmaps.json (frame 0 recorded from the unmodified fisheye.c, the rest from the oracle's
+        # render_lensmap over the reference's lensmap: tests/golden/make_golden.py).  Frame f of that step is LCG globe (g0 + f) % R,
+        # which the goldens cover while R <= 64.  Nothing of the CPU oracle is touched here: the hash is bk_debug_fnv1a64.
+        from concurrent.futures import ThreadPoolExecutor
+        gold = None
+        for rec in json.load(open(os.path.join(ROOT, "tests", "golden", "lensmaps.json")))["lensmaps"]:
+            if (rec["globe"], rec["lens"], rec["W"], rec["H"]) == (GLOBE, LENS, W, H) and rec["zoom"] in (None, ZOOM) and "fnv_frames" in rec:
+                gold, gold_rec = rec["fnv_frames"], rec
+        if gold is None or R > len(gold):
+            sys.exit(f"[check] no golden frames for {W}x{H} {GLOBE}/{LENS} over a ring of {R} globes (tests/golden/lensmaps.json)")
+        g0 = first_globe(last_step)
+        if world > 1:
+            mine = multigpu.owned_frames(F, rank, world) if exchange_mode == "rotating" else []
+            held = {f: frames_out[last_step % NB][f // world] for f in mine}
+        else:
+            ctx.apply_device(origin(stripe), W, rows * W, frame0=g0, nframes=F)      # the timed launch once more, into a buffer read back here
+            torch.cuda.synchronize()
+            held = {f: stripe[f] for f in range(F)}
+            off, tin = ctx.read_lensmap()                  # ... and the table the timed launches gathered through IS the reference's
+            mine_is = (blinky_amd.ffi.fnv1a64(off), blinky_amd.ffi.fnv1a64(tin), repr(scale))
+            if mine_is != (gold_rec["fnv_offsets"], gold_rec["fnv_tints"], gold_rec["scale"]):
+                sys.exit(f"[check] the lensmap this run built differs from the reference's golden: offsets / tints / scale {mine_is} against "
+                         f"{(gold_rec['fnv_offsets'], gold_rec['fnv_tints'], gold_rec['scale'])}")
+            del off, tin
+        with ThreadPoolExecutor(8) as pool:
+            got = dict(zip(held, pool.map(lambda t: blinky_amd.ffi.fnv1a64(t.cpu().numpy()), held.values())))
+        bad = [f for f in held if got[f] != gold[(g0 + f) % R]]
+        print(f"[check] rank {rank}: {'OK' if not bad else 'MISMATCH in frames ' + str(bad)} ({len(held)} frames against tests/golden/lensmaps.json)",
+              file=sys.stderr, flush=True)
+        if bad:
+            sys.exit(3)
+
+    px_per_step = W * H * F
+    value = px_per_step * args.steps / elapsed / 1e6
+    out = {
+        "metric": "warped Mpixels/s (lensmap apply)", "value": round(value, 1), "unit": "Mpixels/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "config": {"workload": f"{W}x{H} {GLOBE}/{LENS} {ZOOM}, {F} frames/step from a resident ring of {R} distinct globes "
+                               f"({R * 6 * 2160 * 2176 / 1e9:.2f} GB, advanced every step), one lensmap; value / ms_per_step = the job with steps "
+                               f"alternating between {nstreams} HIP stream(s), value_one_stream = the same on one stream, roofline.kernel_ms_per_launch "
+                               "= the kernel alone under HIP events; 64 frames/step since r5 (r1-r4 ran 16: compare those with value_at_16_frames)",
+                   "frames_per_step": F, "ring_globes": R,
+                   "parallelism": f"row-stripes x{world}" + ("" if world == 1 else (" + bk_comm (librccl grouped ncclSend/ncclRecv behind the C ABI)" if comm else " + gloo host exchange (developer smoke)" if host_exchange else f" + torch.distributed RCCL send/recv (bk_comm unavailable: {comm_fallback})") +
+                                                                 (": frame f reassembled on rank f%N" if exchange_mode == "rotating" else ": every frame gathered onto rank 0")),
+                   "apply_variant": args.variant, "streams": nstreams,
+                   "streams_note": "consecutive steps alternate between this many HIP streams, so the tail of one batch launch "
+                                   "overlaps the ramp of the next; roofline.* is the kernel alone on one stream"}}
+    if not args.full:
+        if rank == 0:
+            print(compact_line(out), flush=True)
+        finish()
+        return
+
     nrep = args.repeats
     if nrep <= 0:
         # as many regions as keep the GPU busy for --min-gpu-seconds (a 50-step 4K region is ~3 ms: 31 of them would be
         # 0.1 s of GPU work inside a run of several seconds); every rank derives the same count from the max over ranks
-        probe = timed_region(args.warmup)
-        nrep = int(min(20000, max(31, args.min_gpu_seconds / max(probe, 1e-6))))
-    regions = [timed_region(args.warmup + k * args.steps) for k in range(max(1, nrep))]
-    elapsed = statistics.median(regions)
+        nrep = int(min(20000, max(31, args.min_gpu_seconds / max(elapsed, 1e-6))))
+    regions += [timed_region(args.warmup + k * args.steps) for k in range(1, nrep)]
     # the same job with every launch on ONE stream (what roofline.kernel_ms_per_launch is to be compared with)
     one_stream_elapsed = None
     if nstreams > 1:
@@ -959,44 +1088,7 @@ def main():
         except Exception as e:      # noqa: BLE001
             single_resident = {"error": f"{type(e).__name__}: {e}"}
 
-    if args.check:
-        # Every frame this rank ends up holding after the LAST step of the timed region, against the reference: FNV-1a-64 per frame
-        # compared with tests/golden/lensmaps.json (frame 0 recorded from the unmodified fisheye.c, the rest from the oracle's
-        # render_lensmap over the reference's lensmap: tests/golden/make_golden.py).  Frame f of that step is LCG globe (g0 + f) % R,
-        # which the goldens cover while R <= 64.  Nothing of the CPU oracle is touched here: the hash is bk_debug_fnv1a64.
-        from concurrent.futures import ThreadPoolExecutor
-        gold = None
-        for rec in json.load(open(os.path.join(ROOT, "tests", "golden", "lensmaps.json")))["lensmaps"]:
-            if (rec["globe"], rec["lens"], rec["W"], rec["H"]) == (GLOBE, LENS, W, H) and rec["zoom"] in (None, ZOOM) and "fnv_frames" in rec:
-                gold, gold_rec = rec["fnv_frames"], rec
-        if gold is None or R > len(gold):
-            sys.exit(f"[check] no golden frames for {W}x{H} {GLOBE}/{LENS} over a ring of {R} globes (tests/golden/lensmaps.json)")
-        last_i = args.warmup + max(1, nrep // 4 if one_stream_elapsed is not None else nrep) * args.steps - 1   # the last step of the last timed region
-        g0 = first_globe(last_i)
-        if world > 1:
-            mine = multigpu.owned_frames(F, rank, world) if exchange_mode == "rotating" else []
-            held = {f: frames_out[last_i % NB][f // world] for f in mine}
-        else:
-            ctx.apply_device(origin(stripe), W, rows * W, frame0=g0, nframes=F)      # the timed launch once more, into a buffer read back here
-            torch.cuda.synchronize()
-            held = {f: stripe[f] for f in range(F)}
-            off, tin = ctx.read_lensmap()                  # ... and the table the timed launches gathered through IS the reference's
-            mine_is = (blinky_amd.ffi.fnv1a64(off), blinky_amd.ffi.fnv1a64(tin), repr(scale))
-            if mine_is != (gold_rec["fnv_offsets"], gold_rec["fnv_tints"], gold_rec["scale"]):
-                sys.exit(f"[check] the lensmap this run built differs from the reference's golden: offsets / tints / scale {mine_is} against "
-                         f"{(gold_rec['fnv_offsets'], gold_rec['fnv_tints'], gold_rec['scale'])}")
-            del off, tin
-        with ThreadPoolExecutor(8) as pool:
-            got = dict(zip(held, pool.map(lambda t: blinky_amd.ffi.fnv1a64(t.cpu().numpy()), held.values())))
-        bad = [f for f in held if got[f] != gold[(g0 + f) % R]]
-        print(f"[check] rank {rank}: {'OK' if not bad else 'MISMATCH in frames ' + str(bad)} ({len(held)} frames against tests/golden/lensmaps.json)",
-              file=sys.stderr, flush=True)
-        if bad:
-            sys.exit(3)
-
     if rank == 0:
-        px_per_step = W * H * F
-        value = px_per_step * args.steps / elapsed / 1e6
         algo_bytes = ALGO_BYTES_PER_PX * W * rows * F                      # per launch on this rank
         achieved = algo_bytes / (k_med * 1e-3) / 1e9
         # what the kernel has to move per launch: every mapped pixel stored once, every distinct globe line the lensmap
@@ -1042,30 +1134,17 @@ def main():
                           "apply_traffic_is": "traffic (PMC)" if traffic else "compulsory model"}
         except Exception as e:      # noqa: BLE001
             stream_mix = {"error": f"{type(e).__name__}: {e}"}
-        out = {
-            "metric": "warped Mpixels/s (lensmap apply)", "value": round(value, 1), "unit": "Mpixels/s",
+        out.update({
             "value_one_stream": round(px_per_step * args.steps / one_stream_elapsed / 1e6, 1) if one_stream_elapsed else round(value, 1),
             "ms_per_step_one_stream": round(one_stream_elapsed / args.steps * 1e3, 4) if one_stream_elapsed else None,
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
             # (rounds 1-4 reported the N = 1 job in 16-frame steps; the same job, same run)
             "value_at_16_frames": round(W * H * EXTRA_FRAMES * args.steps / elapsed16 / 1e6, 1) if elapsed16 else None,
             # N > 1: the one-GPU job on the same workload (whole frames, same frames per step), timed by rank 0 in this run
             "scaling_reference_mpx_s": round(scaling_reference, 1) if scaling_reference else None,
             "speedup_vs_scaling_reference": round(value / scaling_reference, 3) if scaling_reference else None,
-            "scaling": "strong", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": f"{W}x{H} {GLOBE}/{LENS} {ZOOM}, {F} frames/step from a resident ring of {R} distinct globes "
-                                   f"({R * 6 * 2160 * 2176 / 1e9:.2f} GB, advanced every step), one lensmap; value / ms_per_step = the job with steps "
-                                   f"alternating between {nstreams} HIP stream(s), value_one_stream = the same on one stream, roofline.kernel_ms_per_launch "
-                                   "= the kernel alone under HIP events; 64 frames/step since r5 (r1-r4 ran 16: compare those with value_at_16_frames)",
-                       "frames_per_step": F, "ring_globes": R,
-                       "parallelism": f"row-stripes x{world}" + ("" if world == 1 else (" + bk_comm (librccl grouped ncclSend/ncclRecv behind the C ABI)" if comm else " + gloo host exchange (developer smoke)" if host_exchange else f" + torch.distributed RCCL send/recv (bk_comm unavailable: {comm_fallback})") +
-                                                                     (": frame f reassembled on rank f%N" if exchange_mode == "rotating" else ": every frame gathered onto rank 0")),
-                       "apply_variant": args.variant, "streams": nstreams,
-                       "streams_note": "consecutive steps alternate between this many HIP streams, so the tail of one batch launch "
-                                       "overlaps the ramp of the next; roofline.* is the kernel alone on one stream"},
-            "timed_regions": {"count": len(regions), "steps_each": args.steps, "value_is": "median", "gpu_timed_seconds": round(sum(regions), 3),
-                              "mpx_s_median": round(value, 1),
+            "timed_regions": {"count": len(regions), "steps_each": args.steps, "value_is": "the first region (the headline's)",
+                              "gpu_timed_seconds": round(sum(regions), 3),
+                              "mpx_s_median": round(px_per_step * args.steps / statistics.median(regions) / 1e6, 1),
                               "mpx_s_min": round(px_per_step * args.steps / max(regions) / 1e6, 1),
                               "mpx_s_max": round(px_per_step * args.steps / min(regions) / 1e6, 1)},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1117,7 +1196,7 @@ def main():
             "single_frame_launch_us": round(single_ms * 1e3, 2),
             "single_frame_mpx_s": round(W * rows / (single_ms * 1e-3) / 1e6, 1),
             "lens_scale": scale,
-        }
+        })
         if world == 1 and not args.no_extra:
             # the other configurations BASELINE.json names that fit one GPU, timed by this same run: C2 (1080p stereographic), C3 (4K
             # quincuncial, the inverse-only full-sphere lens), C5 (8K hammer, 64 frames in ONE launch over a ring of 64 distinct 8K
@@ -1155,11 +1234,7 @@ def main():
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         emit(out, args.detail)
-    if comm:
-        comm.synchronize()
-        comm.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -15,6 +15,14 @@ CSRC = os.path.join(ROOT, "blinky_amd", "csrc")
 _cache = {}
 
 
+def _scratch():
+    """compiled emulation objects, kept between runs; one directory per user, since the first user to create a shared one would
+    own it (and the objects loaded from it)"""
+    d = os.path.join(tempfile.gettempdir(), "bk_hostemu-%d" % os.getuid())
+    os.makedirs(d, exist_ok=True)
+    return d
+
+
 def compile_source(src, defines=()):
     """generated source text -> loaded shared object (defines: extra -D options, e.g. a wider BK_LIBM_REL)"""
     key = hashlib.sha1((" ".join(defines) + src + open(os.path.join(CSRC, "bk_device_rt.h")).read() +
@@ -22,8 +30,7 @@ def compile_source(src, defines=()):
                         open(os.path.join(HERE, "emu_driver.inc")).read() + open(os.path.join(HERE, "emu_prelude.h")).read()).encode()).hexdigest()[:16]
     if key in _cache:
         return _cache[key]
-    d = os.path.join(tempfile.gettempdir(), "bk_hostemu")
-    os.makedirs(d, exist_ok=True)
+    d = _scratch()
     cpp, so = os.path.join(d, key + ".cpp"), os.path.join(d, key + ".so")
     if not os.path.exists(so):
         # per-process scratch names + atomic rename: pytest-xdist workers may want the same key at once
@@ -44,8 +51,7 @@ def _field_offsets():
     """byte offsets of the pointer / count fields of BkBuildParams (bk_build_params.h), found by compiling a probe"""
     if "off" in _cache:
         return _cache["off"]
-    d = os.path.join(tempfile.gettempdir(), "bk_hostemu")
-    os.makedirs(d, exist_ok=True)
+    d = _scratch()
     src = os.path.join(d, "offs.%d.c" % os.getpid())
     with open(src, "w") as f:
         f.write('#include <stddef.h>\n#include <stdio.h>\n#include "bk_build_params.h"\nint main(){'

@@ -1,4 +1,4 @@
-"""bench.py's launcher contract, checked without a GPU: a world size that differs from --gpus is refused, and the line the
+"""bench.py's launcher contract, checked without a GPU: a world size that differs from --gpus is refused, --dump-outputs writes a fixed sample, and the line the
 driver parses stays compact whatever the full record holds."""
 import json
 import os
@@ -52,3 +52,34 @@ def test_the_hash_bench_check_uses_is_the_goldens_hash():
         a = rng.integers(0, 256, n, dtype=np.uint8)
         assert blinky_amd.ffi.fnv1a64(a) == O.fnv(a)
     assert blinky_amd.ffi.fnv1a64(np.zeros(0, np.uint8)) == "cbf29ce484222325"
+
+
+def test_dump_outputs_needs_one_gpu():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", "unused"], capture_output=True,
+                       text=True, timeout=120, cwd=ROOT)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and "{" not in r.stdout
+    assert not os.path.exists(os.path.join(ROOT, "unused"))
+
+
+def test_dumped_outputs_are_a_fixed_sample_of_the_last_steps_frames(tmp_path):
+    """bench.dump_outputs on host frames of the headline's size (fewer of them): float32 / float64 files, the same places sampled every
+    time, every frame of the batch reached, the first frame whole"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    frames = torch.from_numpy(np.random.default_rng(5).integers(0, 256, (3, 2160, 3840), dtype=np.uint8))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frames)
+    names = ("last_step_frame0.npy", "last_step_sample.npy", "last_step_sample_index.npy")
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(names)
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        np.testing.assert_array_equal(a[n], np.load(tmp_path / "b" / n))
+    assert a[names[0]].dtype == np.float32 and a[names[1]].dtype == np.float32 and a[names[2]].dtype == np.float64
+    np.testing.assert_array_equal(a[names[0]], frames[0].numpy())
+    idx = a[names[2]].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0) and idx[-1] < frames.numel() and idx[-1] >= 2 * 2160 * 3840
+    np.testing.assert_array_equal(a[names[1]], frames.reshape(-1).numpy()[idx])
+    # at the headline's 64 frames the files weigh the same: the whole first frame plus a sample of fixed length
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64e6

@@ -1,4 +1,4 @@
-"""bench.py end to end on the GPU box: the JSON contract at N=1, and the N>1 control flow (stripe-local
+"""bench.py end to end on the GPU box: the plain run's headline line and --dump-outputs, the --full JSON contract at N=1, and the N>1 control flow (stripe-local
 build, stripe buffers, rotating-root reassembly, double buffering) with two ranks sharing the one GPU over
 gloo - `--check` makes every rank compare each frame it ends up holding with a full-height warp."""
 import json
@@ -35,8 +35,45 @@ def _assert_compact_contract(c, n):
     assert abs(c["roofline"]["frac"] - c["roofline"]["achieved"] / c["roofline"]["peak"]) < 1e-3
 
 
+def test_plain_bench_times_its_steps_and_dumps_the_last_steps_frames(tmp_path):
+    """A plain run (no --full) prints the headline alone, timed over exactly --steps steps; --dump-outputs writes what the last of
+    them computed - the batch's first frame whole and a fixed sample of all 64 frames, float32, under 64 MB - identically in two
+    runs with the same arguments, and that first frame is the reference's (last step 3 of a 64-globe ring starts at globe 0)."""
+    import numpy as np
+    import oracle_ffi as O
+    W, H, F = 3840, 2160, 64
+    gold = [r["fnv_frames"] for r in json.load(open(os.path.join(ROOT, "tests", "golden", "lensmaps.json")))["lensmaps"]
+            if (r["globe"], r["lens"], r["zoom"], r["W"], r["H"]) == ("cube", "panini", None, W, H) and "fnv_frames" in r][0]
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        c = json.loads(r.stdout.rstrip().splitlines()[-1])
+        assert c["metric"] == "warped Mpixels/s (lensmap apply)" and c["unit"] == "Mpixels/s" and c["higher_is_better"] is True
+        assert c["dtype"] == "u8" and c["n_gpus"] == 1 and c["steps"] == 3 and c["warmup"] == 1 and c["config"]["frames_per_step"] == F
+        # value and ms_per_step describe the same 3 steps
+        assert c["value"] > 0 and abs(c["value"] - W * H * F / (c["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * c["value"], c
+        assert not {"roofline", "value_one_stream", "cpu_baseline", "extras", "build_ms"} & set(c), c
+        files = {p.name: np.load(p) for p in d.iterdir()}
+        assert set(files) == {"last_step_frame0.npy", "last_step_sample.npy", "last_step_sample_index.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64e6
+        dumps.append(files)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)
+    frame0, sample, idx = (dumps[0][k] for k in ("last_step_frame0.npy", "last_step_sample.npy", "last_step_sample_index.npy"))
+    assert frame0.shape == (H, W) and O.fnv(frame0.astype(np.uint8)) == gold[0]
+    idx = idx.astype(np.int64)
+    assert len(idx) == len(sample) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < F * H * W
+    assert idx[-1] >= (F - 1) * H * W and np.all(sample == np.round(sample)) and sample.min() >= 0 and sample.max() <= 255
+    first = idx < H * W
+    np.testing.assert_array_equal(sample[first], frame0.reshape(-1)[idx[first]])
+
+
 def test_bench_line_and_check_single_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "3", "--check",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--repeats", "3", "--check",
                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "[check] rank 0: OK" in r.stderr
@@ -116,7 +153,7 @@ def test_bench_line_and_check_single_gpu():
 def test_bench_two_ranks_sharing_the_gpu_reassemble_every_frame():
     env = dict(os.environ, BLINKY_BENCH_BACKEND="gloo", BLINKY_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--frames", "5", "--ring", "10", "--repeats", "2", "--check"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -145,7 +182,7 @@ def test_bench_eight_ranks_sharing_the_gpu():
     the one-GPU scaling reference timed by rank 0) - and the N = 8 compact line the driver parses."""
     env = dict(os.environ, BLINKY_BENCH_BACKEND="gloo", BLINKY_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "2", "--warmup", "1",
            "--frames", "5", "--ring", "10", "--repeats", "2", "--check"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -170,7 +207,7 @@ def test_bench_gpus_flag_launches_its_own_ranks():
     measured one GPU); here both ranks share the one GPU over gloo."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(BLINKY_BENCH_BACKEND="gloo", BLINKY_BENCH_ONE_GPU="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--repeats", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     compact = json.loads(r.stdout.rstrip().splitlines()[-1])
