@@ -1306,16 +1306,24 @@ public:
             if (pooled >= threads_.size() / 2) wake_.notify_all();
             else for (size_t i = 0; i < pooled; ++i) wake_.notify_one();
         }
-        job(pooled);
-        if (pooled) {
-            // (the caller's job returns when the shared counter is used up: workers that have not even woken yet are not waited for -
-            //  their turns are withdrawn - only those that are in the middle of their last piece)
+        // (the caller's job returns when the shared counter is used up: workers that have not even woken yet are not waited for -
+        //  their turns are withdrawn - only those that are in the middle of their last piece; the same when the caller's job throws
+        //  - Interp::clone's std::bad_alloc - so that no worker is left running a job that no longer exists)
+        const auto withdraw = [&] {
+            if (!pooled) return;
             std::unique_lock<std::mutex> lock(m_);
             want_ = next_;
             finished_.wait(lock, [&] { return done_ == want_; });
             job_ = nullptr;
             want_ = next_ = done_ = 0;
+        };
+        try {
+            job(pooled);
+        } catch (...) {
+            withdraw();
+            throw;
         }
+        withdraw();
     }
     ~FixupPool()
     {
@@ -1481,30 +1489,91 @@ static HostModuleP fixup_module(LensProgram *P, const std::string &source)
     return host_module_for(source, bk::g_debug.host_module == 1);
 }
 
-// the flag list a kernel just filled: grows the list and reports `retry` when it overflowed
-static int read_flagged(bk_ctx *ctx, unsigned int count, std::vector<uint32_t> *list, bool *retry)
+// a pass's counters at bk_ctx::d_display: display flags, error bits, flagged-entry count, first malformed result
+constexpr int kNumCounters = BK_MAX_PLATES + 3;
+
+/* the flag list and the pinned counters of the passes below (room for a forward build's two sets) */
+static int alloc_flag_buffers(bk_ctx *ctx)
 {
-    *retry = false;
-    list->clear();
-    if (count > ctx->flag_cap) {
+    if (!ctx->d_flag_list) {
+        BK_HIP(ctx, hipMalloc((void **)&ctx->d_flag_list, (size_t)65536 * 4 * sizeof(uint32_t)));
+        ctx->flag_cap = 65536;
+    }
+    if (!ctx->h_build_flags) BK_HIP(ctx, hipHostMalloc((void **)&ctx->h_build_flags, 2 * kNumCounters * sizeof(int), hipHostMallocDefault));
+    return BK_OK;
+}
+
+/* launch() a pass that may flag entries, read back its counters (pinned: a pageable destination goes through the runtime's staging
+ * buffer) and its flag list, again while the list overflows; the counters are cleared before each launch, the first only if `reset` */
+template <typename Launch>
+static int flagged_pass(bk_ctx *ctx, const char *what, BkBuildParams &bp, bool reset, Launch launch, int counters[kNumCounters],
+                        std::vector<uint32_t> *flagged, int *retries = nullptr)
+{
+    unsigned int count = 0;
+    for (;; reset = true) {
+        if (reset) BK_HIP(ctx, hipMemsetAsync(ctx->d_display, 0, kNumCounters * sizeof(int), ctx->stream));
+        if (hipError_t e = launch()) return ctx->fail(BK_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        BK_HIP(ctx, hipMemcpyAsync(ctx->h_build_flags, ctx->d_display, kNumCounters * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(counters, ctx->h_build_flags, kNumCounters * sizeof(int));
+        count = (unsigned)counters[BK_MAX_PLATES + 1];
+        if (count <= ctx->flag_cap) break;
         (void)hipFree(ctx->d_flag_list);
         ctx->d_flag_list = nullptr;
         ctx->flag_cap = 0;
         const size_t cap = (size_t)count + count / 4 + 1024;
         BK_HIP(ctx, hipMalloc((void **)&ctx->d_flag_list, cap * 4 * sizeof(uint32_t)));
         ctx->flag_cap = cap;
-        *retry = true;
-        return BK_OK;
+        bp.flag_list = ctx->d_flag_list;                   // (nothing else in bp depends on the list)
+        bp.flag_cap = (unsigned)cap;
+        if (retries) ++*retries;
     }
+    flagged->assign((size_t)count * 4, 0u);
     if (!count) return BK_OK;
-    list->resize((size_t)count * 4);
-    BK_HIP(ctx, hipMemcpyAsync(list->data(), ctx->d_flag_list, (size_t)count * 16, hipMemcpyDeviceToHost, ctx->stream));
+    BK_HIP(ctx, hipMemcpyAsync(flagged->data(), ctx->d_flag_list, (size_t)count * 16, hipMemcpyDeviceToHost, ctx->stream));
     BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // The kernels append wave by wave: runs of up to 64 ascending ids.  A short list is put into the reference's scan order outright;
     // a long one (eckert4 flags whole rows: 640 K entries) is left in its runs - sorting it cost more than the re-derivation, and a
     // script's per-row cache is as warm within a run as within the sorted list.
-    if (count <= 131072) sort_flagged(*list);
+    if (count <= 131072) sort_flagged(*flagged);
     return BK_OK;
+}
+
+/* re-derive n entries (entry i is ids[i * stride]) by the compiled host module of `source` if fixup_module gives one, else by the
+ * interpreter; n == 0 or no source looks nothing up.  timed: accounted in last_host_eval_ms / last_fixup_compiled */
+template <typename ModuleCall, typename InterpCall>
+static void rederive(bk_ctx *ctx, LensProgram *P, const std::string &source, const uint32_t *ids, int stride, size_t n, bool timed,
+                     ModuleCall module, InterpCall interp)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const HostModuleP hm = n && !source.empty() ? fixup_module(P, source) : nullptr;
+    if (timed) ctx->last_fixup_compiled = hm != nullptr;
+    if (hm) hostmod_runs(n, [&](size_t i0, size_t cnt) { module(*hm, ids + i0 * stride, stride, (unsigned long)cnt, i0); });
+    else for_each_flagged(P, n, [&](HostEval &E, size_t i) { interp(E, ids[i * stride], i); });
+    if (timed) ctx->last_host_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+/* scatter the re-derived entries that differ from the device's answer (flag record: id, W words, a byte) to words[W * id + j] and
+ * bytes[id]; counted in last_flagged / last_changed */
+template <size_t W>
+static int patch_changed(bk_ctx *ctx, const std::vector<uint32_t> &flagged, const uint32_t *const (&host_words)[W], const uint8_t *host_bytes,
+                         uint32_t *words, uint8_t *bytes)
+{
+    std::vector<uint32_t> iw, vw, ib;
+    std::vector<uint8_t> vb;
+    const size_t nfl = flagged.size() / 4;
+    for (size_t i = 0; i < nfl; ++i) {
+        const uint32_t *rec = &flagged[4 * i];
+        bool same = host_bytes[i] == (uint8_t)rec[1 + W];
+        for (size_t j = 0; j < W; ++j) same = same && host_words[j][i] == rec[1 + j];
+        if (same) continue;
+        for (size_t j = 0; j < W; ++j) { iw.push_back((uint32_t)W * rec[0] + (uint32_t)j); vw.push_back(host_words[j][i]); }
+        ib.push_back(rec[0]); vb.push_back(host_bytes[i]);
+    }
+    ctx->last_flagged = (int)nfl;
+    ctx->last_changed = (int)ib.size();
+    if (int r = bk::launch_scatter32(ctx, words, iw.data(), vw.data(), iw.size())) return r;
+    return bk::launch_scatter8(ctx, bytes, ib.data(), vb.data(), ib.size());
 }
 
 /* Where a host-built table goes: into the context's device lensmap - or, for bk_debug_host_build on a context without a device, into the
@@ -1876,6 +1945,211 @@ extern "C" int bk_lens_carries_state(bk_ctx *ctx, char *global_name, size_t cap)
     return carries ? 1 : 0;
 }
 
+struct HipFree { void operator()(void *p) const { (void)hipFree(p); } };
+using DeviceMem = std::unique_ptr<void, HipFree>;
+
+/* the inverse build on the device; counters: the pass's, with the re-derived entries' display flags, errors and first bad key merged in */
+static int build_inverse_device(bk_ctx *ctx, LensProgram *P, const std::string &src, BkBuildParams &bp, int counters[kNumCounters])
+{
+    if (!P->k_inverse) return ctx->fail(BK_E_STATE, "lens has no lens_inverse (map = \"lens_inverse\" without the function)");
+    for (int k = 0; k < 4; ++k) {                     // (a forward build's scratch is not kept under an inverse lens)
+        (void)hipFree(ctx->fwd_scratch[k]);
+        ctx->fwd_scratch[k] = nullptr; ctx->fwd_scratch_bytes[k] = 0;
+    }
+    void *args[] = {&bp};
+    BK_HIP(ctx, hipEventRecord(ctx->build_time_ev[0], ctx->stream));
+    const auto tk0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> flagged;
+    if (int r = flagged_pass(ctx, "bk_build_inverse launch", bp, false, [&] {
+            return hipModuleLaunchKernel(P->k_inverse, (unsigned)((ctx->W + 255) / 256), (unsigned)ctx->rows(), 1, 256, 1, 1, 0, ctx->stream, args, nullptr);
+        }, counters, &flagged, &ctx->last_kernel_retries)) return r;
+    ctx->last_kernel_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk0).count();
+    // re-derive the flagged pixels on the host and patch the ones that differ
+    const size_t nfl = flagged.size() / 4;
+    std::vector<uint32_t> roff(nfl);
+    std::vector<uint8_t> rtint(nfl);
+    std::vector<int> rshown(nfl), rerr(nfl, 0);
+    rederive(ctx, P, src, flagged.data(), 4, nfl, true,
+             [&](const HostModule &hm, const uint32_t *id, int stride, unsigned long cnt, size_t i) { hm.inverse(&bp, id, stride, cnt, &roff[i], &rtint[i], &rshown[i], &rerr[i]); },
+             [&](HostEval &E, uint32_t id, size_t i) { h_inverse_entry(E, bp, id, &roff[i], &rtint[i], &rshown[i], &rerr[i]); });
+    unsigned int bad_key = (unsigned)counters[BK_MAX_PLATES + 2];
+    for (size_t i = 0; i < nfl; ++i) {
+        counters[BK_MAX_PLATES] |= rerr[i];
+        if (rerr[i] & BK_ERR_RESULT) {
+            const uint32_t o = flagged[4 * i], lyl = o / (uint32_t)ctx->W, lx = o - lyl * (uint32_t)ctx->W;
+            bad_key = std::max(bad_key, (uint32_t)(((uint32_t)ctx->row0 + lyl) * (uint32_t)ctx->W + ((uint32_t)ctx->W - 1u - lx)) + 1u);
+        }
+        if (rshown[i] >= 0) counters[rshown[i]] |= 1;
+    }
+    counters[BK_MAX_PLATES + 2] = (int)bad_key;
+    if (int r = patch_changed(ctx, flagged, {roff.data()}, rtint.data(), ctx->d_offsets, ctx->d_tints)) return r;
+    BK_HIP(ctx, hipEventRecord(ctx->build_time_ev[1], ctx->stream));
+    return BK_OK;
+}
+
+/* the forward build on the device; counters: the quad pass's, with the corner pass's and the host's error bits merged in */
+static int build_forward_device(bk_ctx *ctx, LensProgram *P, const std::string &src, BkBuildParams &bp, int counters[kNumCounters])
+{
+    if (!P->k_corners || !P->k_quads || !P->k_resolve) return ctx->fail(BK_E_STATE, "lens has no lens_forward");
+    const size_t px = (size_t)ctx->W * ctx->rows();
+    const size_t n1 = (size_t)ctx->ps + 1;
+    const size_t ncorner = (size_t)ctx->numplates * n1 * n1;
+    const size_t want[4] = {ncorner * 2 * sizeof(int), ncorner, px * 4, px * 4};
+    for (int k = 0; k < 4; ++k)
+        if (ctx->fwd_scratch_bytes[k] < want[k]) {
+            (void)hipFree(ctx->fwd_scratch[k]);
+            ctx->fwd_scratch[k] = nullptr; ctx->fwd_scratch_bytes[k] = 0;
+            BK_HIP(ctx, hipMalloc(&ctx->fwd_scratch[k], want[k]));
+            ctx->fwd_scratch_bytes[k] = want[k];
+        }
+    bp.corner_xy = (int *)ctx->fwd_scratch[0];
+    bp.corner_ok = (unsigned char *)ctx->fwd_scratch[1];
+    bp.fwd_key_px = (unsigned int *)ctx->fwd_scratch[2];
+    bp.fwd_key_tint = (unsigned int *)ctx->fwd_scratch[3];
+    // the quotient / uv tables of bk_build_params.h: plain IEEE divisions, done here once per platesize instead of per texel
+    constexpr size_t NQ = 21 * 21;
+    const size_t ntile = ((size_t)ctx->ps + 15) / 16;              // (BK_FWD_TILE = 16; the tile flags of bk_forward_tiles live behind the tables)
+    if (ctx->fwd_tables_ps != ctx->ps) {
+        (void)hipFree(ctx->fwd_tables);
+        ctx->fwd_tables = nullptr; ctx->fwd_tables_ps = -1;
+        std::vector<double> q(NQ, 0.0);
+        for (int a = 0; a <= 20; ++a)
+            for (int d = 1; d <= 20; ++d) q[(size_t)a * 21 + d] = (double)a / (double)d;
+        std::vector<float> uv(2 * n1);
+        for (size_t i = 0; i < n1; ++i) {
+            uv[i] = (float)(((double)i - 0.5) / ctx->ps - 0.5);
+            uv[n1 + i] = (float)((double)i / ctx->ps - 0.5);
+        }
+        BK_HIP(ctx, hipMalloc(&ctx->fwd_tables, NQ * sizeof(double) + uv.size() * sizeof(float) + (size_t)BK_MAX_PLATES * ntile * ntile));
+        BK_HIP(ctx, hipMemcpy(ctx->fwd_tables, q.data(), NQ * sizeof(double), hipMemcpyHostToDevice));
+        BK_HIP(ctx, hipMemcpy((char *)ctx->fwd_tables + NQ * sizeof(double), uv.data(), uv.size() * sizeof(float), hipMemcpyHostToDevice));
+        ctx->fwd_tables_ps = ctx->ps;
+    }
+    bp.fwd_quot = (const double *)ctx->fwd_tables;
+    bp.fwd_uv = (const float *)((const char *)ctx->fwd_tables + NQ * sizeof(double));
+    unsigned char *const tile_own = (unsigned char *)ctx->fwd_tables + NQ * sizeof(double) + 2 * n1 * sizeof(float);
+    const hipEvent_t e0 = ctx->build_time_ev[0], e1 = ctx->build_time_ev[1];
+    void *args[] = {&bp};
+    const auto clear_keys = [&](hipStream_t st) -> hipError_t {
+        hipError_t e = hipMemsetAsync(ctx->fwd_scratch[2], 0, px * 4, st);
+        return e == hipSuccess ? hipMemsetAsync(ctx->fwd_scratch[3], 0, px * 4, st) : e;
+    };
+    const auto launch_corners = [&] {
+        return hipModuleLaunchKernel(P->k_corners, (unsigned)((n1 + 255) / 256), (unsigned)n1, (unsigned)ctx->numplates, 256, 1, 1, 0, ctx->stream, args, nullptr);
+    };
+    const auto launch_quads = [&](bool keys_cleared = false, void **with = nullptr) -> hipError_t {
+        hipError_t e = keys_cleared ? hipSuccess : clear_keys(ctx->stream);
+        if (e == hipSuccess) e = hipModuleLaunchKernel(P->k_quads, (unsigned)((ctx->ps + 15) / 16), (unsigned)((ctx->ps + 15) / 16), (unsigned)ctx->numplates, 256, 1, 1, 0,
+                                                       ctx->stream, with ? with : args, nullptr);       // (BK_FWD_TILE = 16: bk_build_kernels.h)
+        return e;
+    };
+    const auto launch_resolve = [&](void **with = nullptr) -> hipError_t {
+        return hipModuleLaunchKernel(P->k_resolve, (unsigned)((px + 255) / 256), 1, 1, 256, 1, 1, 0, ctx->stream, with ? with : args, nullptr);
+    };
+    // The three passes in one go, each of the first two counting into its own set of counters, both sets left in pinned memory
+    // by the last pass: nearly every build flags nothing - no corner and no texel for the host
+    // to look at again - and then the table is final when the stream drains, two stops (a read-back and a decision each, 25-30 us
+    // apiece at 4K) earlier.  A build that did flag something is done over the careful way below, and so is the next build of
+    // the same lens.
+    if (!P->fwd_needs_host && !bk::g_debug.forward_careful) {
+        int *const after_corners = ctx->h_build_flags, *const after_quads = ctx->h_build_flags + kNumCounters;
+        if (!ctx->build_aux) {
+            BK_HIP(ctx, hipStreamCreateWithFlags(&ctx->build_aux, hipStreamNonBlocking));
+            for (hipEvent_t &e : ctx->build_ev) BK_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        BK_HIP(ctx, hipEventRecord(e0, ctx->stream));
+        BK_HIP(ctx, hipEventRecord(ctx->build_ev[0], ctx->stream));
+        BK_HIP(ctx, launch_corners());
+        // the key planes (66 MB at 4K) are cleared on the side stream while the corner pass - arithmetic only - has the chip
+        // (after whatever the stream held before this build, which may still read them: build_ev[0])
+        BK_HIP(ctx, hipStreamWaitEvent(ctx->build_aux, ctx->build_ev[0], 0));
+        BK_HIP(ctx, clear_keys(ctx->build_aux));
+        // ... and the tiles that lie wholly inside their plate's own region are found there too (the plates may have changed
+        // since the last build: 110 K threads, a few microseconds)
+        BkBuildParams bq = bp;
+        if (P->k_tiles) {
+            unsigned char *flags_out = tile_own;
+            void *args_t[] = {&bp, &flags_out};
+            BK_HIP(ctx, hipModuleLaunchKernel(P->k_tiles, (unsigned)((ntile * ntile + 255) / 256), (unsigned)ctx->numplates, 1, 256, 1, 1, 0, ctx->build_aux, args_t, nullptr));
+            bq.tile_own = tile_own;
+            ctx->fwd_tiles_used = true;
+        }
+        BK_HIP(ctx, hipEventRecord(ctx->build_ev[1], ctx->build_aux));
+        bq.display = ctx->d_display + kNumCounters;       // the quad pass counts into the second set (cleared with the first by bk_build)
+        bq.err = bq.display + BK_MAX_PLATES;
+        bq.flag_count = (unsigned int *)(bq.display + BK_MAX_PLATES + 1);
+        bq.first_bad = (unsigned int *)(bq.display + BK_MAX_PLATES + 2);
+        void *args_q[] = {&bq};
+        BK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->build_ev[1], 0));
+        BK_HIP(ctx, launch_quads(true, args_q));
+        static_assert(2 * kNumCounters == 18, "bk_forward_resolve copies 18 counters");
+        BkBuildParams br = bp;
+        br.counters_out = ctx->h_build_flags;
+        void *args_r[] = {&br};
+        BK_HIP(ctx, launch_resolve(args_r));
+        BK_HIP(ctx, hipEventRecord(e1, ctx->stream));
+        BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (after_corners[BK_MAX_PLATES + 1] == 0 && after_quads[BK_MAX_PLATES + 1] == 0) {
+            memcpy(counters, after_quads, kNumCounters * sizeof(int));
+            counters[BK_MAX_PLATES] |= after_corners[BK_MAX_PLATES];
+            ctx->last_flagged = 0;
+            ctx->last_changed = 0;
+            return BK_OK;
+        }
+        P->fwd_needs_host = true;
+        ctx->fwd_tiles_used = false;
+        BK_HIP(ctx, hipMemsetAsync(ctx->d_display, 0, kNumCounters * sizeof(int), ctx->stream));
+    }
+    BK_HIP(ctx, hipEventRecord(e0, ctx->stream));
+    // texel corners -> screen; the flagged ones re-derived on the host
+    std::vector<uint32_t> flagged;
+    if (int r = flagged_pass(ctx, "bk_forward_corners launch", bp, false, launch_corners, counters, &flagged)) return r;
+    const size_t nfl = flagged.size() / 4;
+    std::vector<int> rsx(nfl), rsy(nfl), rerr(nfl, 0);
+    std::vector<uint8_t> rok(nfl);
+    rederive(ctx, P, src, flagged.data(), 4, nfl, true,
+             [&](const HostModule &hm, const uint32_t *id, int stride, unsigned long cnt, size_t i) { hm.corners(&bp, id, stride, cnt, &rsx[i], &rsy[i], &rok[i], &rerr[i]); },
+             [&](HostEval &E, uint32_t id, size_t i) { h_corner_entry(ctx, E, bp, id, &rsx[i], &rsy[i], &rok[i], &rerr[i]); });
+    int corner_err = counters[BK_MAX_PLATES];
+    for (int e : rerr) corner_err |= e;
+    if (int r = patch_changed(ctx, flagged, {(const uint32_t *)rsx.data(), (const uint32_t *)rsy.data()}, rok.data(), (uint32_t *)bp.corner_xy, bp.corner_ok)) return r;
+    // quads; with a globe_plate script a texel's "own plate" test can be flagged too: the host answers those, and if an answer
+    // differs from the device's the pass runs once more with the host's answers in place (flagging nothing then)
+    if (int r = flagged_pass(ctx, "bk_forward_quads launch", bp, true, launch_quads, counters, &flagged)) return r;
+    DeviceMem d_ovr;
+    if (!flagged.empty()) {
+        const size_t nown = flagged.size() / 4;
+        std::vector<uint8_t> rown(nown);
+        rederive(ctx, P, src, flagged.data(), 4, nown, false,
+                 [&](const HostModule &hm, const uint32_t *id, int stride, unsigned long cnt, size_t i) { hm.texel_owns(&bp, id, stride, cnt, &rown[i]); },
+                 [&](HostEval &E, uint32_t id, size_t i) { rown[i] = h_texel_owns(ctx, E, bp, id) ? 1 : 0; });
+        std::vector<uint32_t> ovr(nown);                  // texel id << 1 | the host's answer
+        int changed = 0;
+        for (size_t i = 0; i < nown; ++i) {
+            const uint32_t own = rown[i] ? 1u : 0u;
+            changed += own != flagged[4 * i + 1];
+            ovr[i] = flagged[4 * i] << 1 | own;
+        }
+        ctx->last_flagged += (int)nown;
+        ctx->last_changed += changed;
+        if (changed) {
+            std::sort(ovr.begin(), ovr.end());
+            void *d = nullptr;
+            BK_HIP(ctx, hipMalloc(&d, ovr.size() * 4));
+            d_ovr.reset(d);
+            BK_HIP(ctx, hipMemcpyAsync(d, ovr.data(), ovr.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+            bp.ovr_list = (const unsigned int *)d;
+            bp.ovr_count = (unsigned)ovr.size();
+            if (int r = flagged_pass(ctx, "bk_forward_quads launch", bp, true, launch_quads, counters, &flagged)) return r;
+        }
+    }
+    counters[BK_MAX_PLATES] |= corner_err;
+    BK_HIP(ctx, launch_resolve());
+    BK_HIP(ctx, hipEventRecord(e1, ctx->stream));
+    P->fwd_needs_host = ctx->last_flagged != 0;
+    return BK_OK;
+}
+
 extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *scale_out)
 {
     if (!ctx) return BK_E_INVALID;
@@ -1896,7 +2170,7 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
         void now() { if (armed) { (void)hipMemsetAsync(ctx->d_offsets, 0xFF, px * 4, ctx->stream); (void)hipMemsetAsync(ctx->d_tints, 255, px, ctx->stream); armed = false; } }
         ~EmptyUnlessBuilt() { now(); }
     } empty_unless_built{ctx, px};
-    BK_HIP(ctx, hipMemsetAsync(ctx->d_display, 0, 2 * (BK_MAX_PLATES + 3) * sizeof(int), ctx->stream));      // (two sets of counters: see the forward build)
+    BK_HIP(ctx, hipMemsetAsync(ctx->d_display, 0, 2 * kNumCounters * sizeof(int), ctx->stream));      // (two sets of counters: see the forward build)
     ctx->lensmap_valid = true;
     ctx->last_bad_key = 0;
     ctx->spans_valid = false;
@@ -1928,10 +2202,7 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
     if (int r = generate_source(ctx, P, &src, &refused)) return r;
     if (!refused.empty()) { empty_unless_built.now(); return build_on_host(ctx, P, refused, display_out); }     // callbacks the emitter declines: the interpreter evaluates them
     if (int r = compile_module(ctx, P, src)) return r;
-    if (!ctx->d_flag_list) {
-        BK_HIP(ctx, hipMalloc((void **)&ctx->d_flag_list, (size_t)65536 * 4 * sizeof(uint32_t)));
-        ctx->flag_cap = 65536;
-    }
+    if (int r = alloc_flag_buffers(ctx)) return r;
 
     BkBuildParams bp;
     fill_params(ctx, &bp);
@@ -1951,307 +2222,30 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
             return build_forward_host(ctx, P, bp, true, display_out);
         }
     }
-    void *args[] = {&bp};
-    hipEvent_t e0, e1;
     for (hipEvent_t &e : ctx->build_time_ev) if (!e) BK_HIP(ctx, hipEventCreate(&e));
-    e0 = ctx->build_time_ev[0]; e1 = ctx->build_time_ev[1];
-    void *scratch[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int rc = BK_OK;
-    auto cleanup = [&]() {
-        for (void *p : scratch) if (p) (void)hipFree(p);
-    };
-#define BK_HIP_C(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = ctx->fail(BK_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return rc; } } while (0)
-#define BK_RC_C(expr) do { rc = (expr); if (rc != BK_OK) { cleanup(); return rc; } } while (0)
-    int flags[BK_MAX_PLATES + 3];
-    unsigned int host_bad_key = 0;                     // (the same, among the entries the host re-derived)
-    int host_display[BK_MAX_PLATES] = {0, 0, 0, 0, 0, 0};
-    int host_err = 0;
-    std::vector<uint32_t> flagged;
-    auto reset_counters = [&]() -> hipError_t { return hipMemsetAsync(ctx->d_display, 0, (BK_MAX_PLATES + 3) * sizeof(int), ctx->stream); };
-    if (!ctx->h_build_flags) BK_HIP_C(hipHostMalloc((void **)&ctx->h_build_flags, 2 * sizeof flags, hipHostMallocDefault));
-    auto read_counters = [&]() -> hipError_t {       // (into pinned memory: a pageable destination goes through the runtime's staging buffer)
-        hipError_t e = hipMemcpyAsync(ctx->h_build_flags, ctx->d_display, sizeof flags, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) memcpy(flags, ctx->h_build_flags, sizeof flags);
-        return e;
-    };
-
+    int counters[kNumCounters];
     try {
-        if (P->info.map_type == BK_MAP_INVERSE) {
-            if (!P->k_inverse) { cleanup(); return ctx->fail(BK_E_STATE, "lens has no lens_inverse (map = \"lens_inverse\" without the function)"); }
-            for (int k = 0; k < 4; ++k) {                     // (a forward build's scratch is not kept under an inverse lens)
-                (void)hipFree(ctx->fwd_scratch[k]);
-                ctx->fwd_scratch[k] = nullptr; ctx->fwd_scratch_bytes[k] = 0;
-            }
-            BK_HIP_C(hipEventRecord(e0, ctx->stream));
-            const auto tk0 = std::chrono::steady_clock::now();
-            for (;;) {
-                BK_HIP_C(hipModuleLaunchKernel(P->k_inverse, (unsigned)((ctx->W + 255) / 256), (unsigned)ctx->rows(), 1, 256, 1, 1, 0, ctx->stream, args, nullptr));
-                BK_HIP_C(read_counters());
-                bool retry = false;
-                BK_RC_C(read_flagged(ctx, (unsigned)flags[BK_MAX_PLATES + 1], &flagged, &retry));
-                if (!retry) break;
-                ++ctx->last_kernel_retries;
-                fill_params(ctx, &bp);                       // (the list moved)
-                BK_HIP_C(reset_counters());
-            }
-            ctx->last_kernel_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk0).count();
-            // re-derive the flagged pixels on the host and patch the ones that differ
-            std::vector<uint32_t> idx, voff;
-            std::vector<uint8_t> vtint;
-            const size_t nfl = flagged.size() / 4;
-            {
-                std::vector<uint32_t> roff(nfl);
-                std::vector<uint8_t> rtint(nfl);
-                std::vector<int> rshown(nfl), rerr(nfl, 0);
-                const auto th0 = std::chrono::steady_clock::now();
-                const HostModuleP hm = nfl ? fixup_module(P, src) : nullptr;
-                ctx->last_fixup_compiled = hm != nullptr;
-                if (hm) hostmod_runs(nfl, [&](size_t i0, size_t cnt) {
-                    hm->inverse(&bp, &flagged[4 * i0], 4, (unsigned long)cnt, &roff[i0], &rtint[i0], &rshown[i0], &rerr[i0]);
-                });
-                else for_each_flagged(P, nfl, [&](HostEval &E, size_t i) {
-                    h_inverse_entry(E, bp, flagged[4 * i], &roff[i], &rtint[i], &rshown[i], &rerr[i]);
-                });
-                ctx->last_host_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
-                for (size_t i = 0; i < nfl; ++i) {
-                    host_err |= rerr[i];
-                    if (rerr[i] & BK_ERR_RESULT) {
-                        const uint32_t o = flagged[4 * i], lyl = o / (uint32_t)ctx->W, lx = o - lyl * (uint32_t)ctx->W;
-                        host_bad_key = std::max(host_bad_key, (uint32_t)(((uint32_t)ctx->row0 + lyl) * (uint32_t)ctx->W + ((uint32_t)ctx->W - 1u - lx)) + 1u);
-                    }
-                    if (rshown[i] >= 0) host_display[rshown[i]] = 1;
-                    if (roff[i] != flagged[4 * i + 1] || rtint[i] != (uint8_t)flagged[4 * i + 2]) {
-                        idx.push_back(flagged[4 * i]); voff.push_back(roff[i]); vtint.push_back(rtint[i]);
-                    }
-                }
-            }
-            ctx->last_flagged = (int)nfl;
-            ctx->last_changed = (int)idx.size();
-            BK_RC_C(bk::launch_scatter32(ctx, ctx->d_offsets, idx.data(), voff.data(), idx.size()));
-            BK_RC_C(bk::launch_scatter8(ctx, ctx->d_tints, idx.data(), vtint.data(), idx.size()));
-            BK_HIP_C(hipEventRecord(e1, ctx->stream));
-        } else {
-            if (!P->k_corners || !P->k_quads || !P->k_resolve) { cleanup(); return ctx->fail(BK_E_STATE, "lens has no lens_forward"); }
-            const size_t n1 = (size_t)ctx->ps + 1;
-            const size_t ncorner = (size_t)ctx->numplates * n1 * n1;
-            const size_t want[4] = {ncorner * 2 * sizeof(int), ncorner, px * 4, px * 4};
-            for (int k = 0; k < 4; ++k)
-                if (ctx->fwd_scratch_bytes[k] < want[k]) {
-                    (void)hipFree(ctx->fwd_scratch[k]);
-                    ctx->fwd_scratch[k] = nullptr; ctx->fwd_scratch_bytes[k] = 0;
-                    BK_HIP_C(hipMalloc(&ctx->fwd_scratch[k], want[k]));
-                    ctx->fwd_scratch_bytes[k] = want[k];
-                }
-            bp.corner_xy = (int *)ctx->fwd_scratch[0];
-            bp.corner_ok = (unsigned char *)ctx->fwd_scratch[1];
-            bp.fwd_key_px = (unsigned int *)ctx->fwd_scratch[2];
-            bp.fwd_key_tint = (unsigned int *)ctx->fwd_scratch[3];
-            // the quotient / uv tables of bk_build_params.h: plain IEEE divisions, done here once per platesize instead of per texel
-            constexpr size_t NQ = 21 * 21;
-            const size_t ntile = ((size_t)ctx->ps + 15) / 16;              // (BK_FWD_TILE = 16; the tile flags of bk_forward_tiles live behind the tables)
-            if (ctx->fwd_tables_ps != ctx->ps) {
-                (void)hipFree(ctx->fwd_tables);
-                ctx->fwd_tables = nullptr; ctx->fwd_tables_ps = -1;
-                std::vector<double> q(NQ, 0.0);
-                for (int a = 0; a <= 20; ++a)
-                    for (int d = 1; d <= 20; ++d) q[(size_t)a * 21 + d] = (double)a / (double)d;
-                std::vector<float> uv(2 * n1);
-                for (size_t i = 0; i < n1; ++i) {
-                    uv[i] = (float)(((double)i - 0.5) / ctx->ps - 0.5);
-                    uv[n1 + i] = (float)((double)i / ctx->ps - 0.5);
-                }
-                BK_HIP_C(hipMalloc(&ctx->fwd_tables, NQ * sizeof(double) + uv.size() * sizeof(float) + (size_t)BK_MAX_PLATES * ntile * ntile));
-                BK_HIP_C(hipMemcpy(ctx->fwd_tables, q.data(), NQ * sizeof(double), hipMemcpyHostToDevice));
-                BK_HIP_C(hipMemcpy((char *)ctx->fwd_tables + NQ * sizeof(double), uv.data(), uv.size() * sizeof(float), hipMemcpyHostToDevice));
-                ctx->fwd_tables_ps = ctx->ps;
-            }
-            bp.fwd_quot = (const double *)ctx->fwd_tables;
-            bp.fwd_uv = (const float *)((const char *)ctx->fwd_tables + NQ * sizeof(double));
-            unsigned char *const tile_own = (unsigned char *)ctx->fwd_tables + NQ * sizeof(double) + 2 * n1 * sizeof(float);
-            const auto clear_keys = [&](hipStream_t st) -> hipError_t {
-                hipError_t e = hipMemsetAsync(ctx->fwd_scratch[2], 0, px * 4, st);
-                return e == hipSuccess ? hipMemsetAsync(ctx->fwd_scratch[3], 0, px * 4, st) : e;
-            };
-            const auto launch_quads = [&](bool keys_cleared = false, void **with = nullptr) -> hipError_t {
-                hipError_t e = keys_cleared ? hipSuccess : clear_keys(ctx->stream);
-                if (e == hipSuccess) e = hipModuleLaunchKernel(P->k_quads, (unsigned)((ctx->ps + 15) / 16), (unsigned)((ctx->ps + 15) / 16), (unsigned)ctx->numplates, 256, 1, 1, 0,
-                                                               ctx->stream, with ? with : args, nullptr);       // (BK_FWD_TILE = 16: bk_build_kernels.h)
-                return e;
-            };
-            const auto launch_resolve = [&](void **with = nullptr) -> hipError_t {
-                return hipModuleLaunchKernel(P->k_resolve, (unsigned)((px + 255) / 256), 1, 1, 256, 1, 1, 0, ctx->stream, with ? with : args, nullptr);
-            };
-            // The three passes in one go, each of the first two counting into its own set of counters, both sets left in pinned memory
-            // by the last pass: nearly every build flags nothing - no corner and no texel for the host
-            // to look at again - and then the table is final when the stream drains, two stops (a read-back and a decision each, 25-30 us
-            // apiece at 4K) earlier.  A build that did flag something is done over the careful way below, and so is the next build of
-            // the same lens.
-            bool speculated = false;
-            if (!P->fwd_needs_host && !bk::g_debug.forward_careful) {
-                constexpr size_t NF = BK_MAX_PLATES + 3;
-                int *const after_corners = ctx->h_build_flags, *const after_quads = ctx->h_build_flags + NF;
-                if (!ctx->build_aux) {
-                    BK_HIP_C(hipStreamCreateWithFlags(&ctx->build_aux, hipStreamNonBlocking));
-                    for (hipEvent_t &e : ctx->build_ev) BK_HIP_C(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                }
-                BK_HIP_C(hipEventRecord(e0, ctx->stream));
-                BK_HIP_C(hipEventRecord(ctx->build_ev[0], ctx->stream));
-                BK_HIP_C(hipModuleLaunchKernel(P->k_corners, (unsigned)((n1 + 255) / 256), (unsigned)n1, (unsigned)ctx->numplates, 256, 1, 1, 0, ctx->stream, args, nullptr));
-                // the key planes (66 MB at 4K) are cleared on the side stream while the corner pass - arithmetic only - has the chip
-                // (after whatever the stream held before this build, which may still read them: build_ev[0])
-                BK_HIP_C(hipStreamWaitEvent(ctx->build_aux, ctx->build_ev[0], 0));
-                BK_HIP_C(clear_keys(ctx->build_aux));
-                // ... and the tiles that lie wholly inside their plate's own region are found there too (the plates may have changed
-                // since the last build: 110 K threads, a few microseconds)
-                BkBuildParams bq = bp;
-                if (P->k_tiles) {
-                    unsigned char *flags_out = tile_own;
-                    void *args_t[] = {&bp, &flags_out};
-                    BK_HIP_C(hipModuleLaunchKernel(P->k_tiles, (unsigned)((ntile * ntile + 255) / 256), (unsigned)ctx->numplates, 1, 256, 1, 1, 0, ctx->build_aux, args_t, nullptr));
-                    bq.tile_own = tile_own;
-                    ctx->fwd_tiles_used = true;
-                }
-                BK_HIP_C(hipEventRecord(ctx->build_ev[1], ctx->build_aux));
-                bq.display = ctx->d_display + NF;            // the quad pass counts into the second set (cleared with the first, above)
-                bq.err = bq.display + BK_MAX_PLATES;
-                bq.flag_count = (unsigned int *)(bq.display + BK_MAX_PLATES + 1);
-                bq.first_bad = (unsigned int *)(bq.display + BK_MAX_PLATES + 2);
-                void *args_q[] = {&bq};
-                BK_HIP_C(hipStreamWaitEvent(ctx->stream, ctx->build_ev[1], 0));
-                BK_HIP_C(launch_quads(true, args_q));
-                static_assert(2 * NF == 18, "bk_forward_resolve copies 18 counters");
-                BkBuildParams br = bp;
-                br.counters_out = ctx->h_build_flags;
-                void *args_r[] = {&br};
-                BK_HIP_C(launch_resolve(args_r));
-                BK_HIP_C(hipEventRecord(e1, ctx->stream));
-                BK_HIP_C(hipStreamSynchronize(ctx->stream));
-                if (after_corners[BK_MAX_PLATES + 1] == 0 && after_quads[BK_MAX_PLATES + 1] == 0) {
-                    memcpy(flags, after_quads, sizeof flags);
-                    flags[BK_MAX_PLATES] |= after_corners[BK_MAX_PLATES];
-                    ctx->last_flagged = 0;
-                    ctx->last_changed = 0;
-                    speculated = true;
-                } else {
-                    P->fwd_needs_host = true;
-                    ctx->fwd_tiles_used = false;
-                    BK_HIP_C(reset_counters());
-                }
-            }
-            if (!speculated) {
-                BK_HIP_C(hipEventRecord(e0, ctx->stream));
-                // texel corners -> screen; the flagged ones re-derived on the host
-                for (;;) {
-                    BK_HIP_C(hipModuleLaunchKernel(P->k_corners, (unsigned)((n1 + 255) / 256), (unsigned)n1, (unsigned)ctx->numplates, 256, 1, 1, 0, ctx->stream, args, nullptr));
-                    BK_HIP_C(read_counters());
-                    bool retry = false;
-                    BK_RC_C(read_flagged(ctx, (unsigned)flags[BK_MAX_PLATES + 1], &flagged, &retry));
-                    if (!retry) break;
-                    bp.flag_list = ctx->d_flag_list; bp.flag_cap = (unsigned)ctx->flag_cap;
-                    BK_HIP_C(reset_counters());
-                }
-                int corner_err = flags[BK_MAX_PLATES];
-                {
-                    std::vector<uint32_t> ixy, vxy, iok;
-                    std::vector<uint8_t> vok;
-                    const size_t nfl = flagged.size() / 4;
-                    std::vector<int> rsx(nfl), rsy(nfl), rerr(nfl, 0);
-                    std::vector<uint8_t> rok(nfl);
-                    const auto th0 = std::chrono::steady_clock::now();
-                    const HostModuleP hm = nfl ? fixup_module(P, src) : nullptr;
-                    ctx->last_fixup_compiled = hm != nullptr;
-                    if (hm) hostmod_runs(nfl, [&](size_t i0, size_t cnt) {
-                        hm->corners(&bp, &flagged[4 * i0], 4, (unsigned long)cnt, &rsx[i0], &rsy[i0], &rok[i0], &rerr[i0]);
-                    });
-                    else for_each_flagged(P, nfl, [&](HostEval &E, size_t i) {
-                        h_corner_entry(ctx, E, bp, flagged[4 * i], &rsx[i], &rsy[i], &rok[i], &rerr[i]);
-                    });
-                    ctx->last_host_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
-                    for (size_t i = 0; i < nfl; ++i) {
-                        const size_t k = 4 * i;
-                        const int sx = rsx[i], sy = rsy[i];
-                        const uint8_t ok = rok[i];
-                        host_err |= rerr[i];
-                        if ((uint32_t)sx != flagged[k + 1] || (uint32_t)sy != flagged[k + 2] || ok != (uint8_t)flagged[k + 3]) {
-                            ixy.push_back(2 * flagged[k]); vxy.push_back((uint32_t)sx);
-                            ixy.push_back(2 * flagged[k] + 1); vxy.push_back((uint32_t)sy);
-                            iok.push_back(flagged[k]); vok.push_back(ok);
-                        }
-                    }
-                    ctx->last_flagged = (int)(flagged.size() / 4);
-                    ctx->last_changed = (int)iok.size();
-                    BK_RC_C(bk::launch_scatter32(ctx, (uint32_t *)bp.corner_xy, ixy.data(), vxy.data(), ixy.size()));
-                    BK_RC_C(bk::launch_scatter8(ctx, bp.corner_ok, iok.data(), vok.data(), iok.size()));
-                }
-                // quads; with a globe_plate script a texel's "own plate" test can be flagged too: the host answers those and
-                // the scatter runs once more with its answers
-                std::vector<uint32_t> ovr;
-                for (int pass = 0; pass < 2; ++pass) {
-                    bool again = false;
-                    for (;;) {
-                        BK_HIP_C(reset_counters());
-                        BK_HIP_C(launch_quads());
-                        BK_HIP_C(read_counters());
-                        if (pass == 1) break;
-                        bool retry = false;
-                        BK_RC_C(read_flagged(ctx, (unsigned)flags[BK_MAX_PLATES + 1], &flagged, &retry));
-                        if (!retry) break;
-                        bp.flag_list = ctx->d_flag_list; bp.flag_cap = (unsigned)ctx->flag_cap;
-                    }
-                    if (pass == 0 && !flagged.empty()) {
-                        std::vector<std::pair<uint32_t, uint32_t>> ans;
-                        const size_t nfl = flagged.size() / 4;
-                        std::vector<uint8_t> rown(nfl);
-                        const HostModuleP hm = fixup_module(P, src);
-                        if (hm) hostmod_runs(nfl, [&](size_t i0, size_t cnt) { hm->texel_owns(&bp, &flagged[4 * i0], 4, (unsigned long)cnt, &rown[i0]); });
-                        else for_each_flagged(P, nfl, [&](HostEval &E, size_t i) { rown[i] = h_texel_owns(ctx, E, bp, flagged[4 * i]) ? 1 : 0; });
-                        for (size_t k = 0; k + 3 < flagged.size(); k += 4) {
-                            const bool own = rown[k / 4] != 0;
-                            if ((own ? 1u : 0u) != flagged[k + 1]) { again = true; ++ctx->last_changed; }
-                            ans.push_back({flagged[k], own ? 1u : 0u});
-                        }
-                        ctx->last_flagged += (int)ans.size();
-                        if (again) {
-                            std::sort(ans.begin(), ans.end());
-                            for (auto &a : ans) { ovr.push_back((a.first << 1) | a.second); }
-                            BK_HIP_C(hipMalloc(&scratch[4], ovr.size() * 4));
-                            BK_HIP_C(hipMemcpyAsync(scratch[4], ovr.data(), ovr.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-                            bp.ovr_list = (const unsigned int *)scratch[4];
-                            bp.ovr_count = (unsigned)ovr.size();
-                        }
-                    }
-                    if (!again) break;
-                }
-                flags[BK_MAX_PLATES] |= corner_err;
-                BK_HIP_C(launch_resolve());
-                BK_HIP_C(hipEventRecord(e1, ctx->stream));
-                P->fwd_needs_host = ctx->last_flagged != 0;
-            }
-        }
+        const bool inverse = P->info.map_type == BK_MAP_INVERSE;
+        if (int r = inverse ? build_inverse_device(ctx, P, src, bp, counters) : build_forward_device(ctx, P, src, bp, counters)) return r;
     } catch (const LuaError &e) {
-        cleanup();
         return ctx->fail(BK_E_SCRIPT, "lensmap build: %s", e.what());
     }
-    BK_HIP_C(hipStreamSynchronize(ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventElapsedTime(&ms, ctx->build_time_ev[0], ctx->build_time_ev[1]);
     ctx->last_build_ms = ms;
-    cleanup();
-#undef BK_HIP_C
-#undef BK_RC_C
     for (int i = 0; i < BK_MAX_PLATES; ++i) {
-        ctx->display[i] = i < ctx->numplates ? (flags[i] | host_display[i]) : 0;
+        ctx->display[i] = i < ctx->numplates ? counters[i] : 0;
         if (display_out) display_out[i] = ctx->display[i];
     }
-    const int errbits = flags[BK_MAX_PLATES] | host_err;
+    const int errbits = counters[BK_MAX_PLATES];
     if (errbits == BK_ERR_RESULT && P->info.map_type == BK_MAP_INVERSE) {
         // A malformed callback result (status -1) ends the reference's scan at that pixel and KEEPS what it had set by then
         // (fisheye.c:2113-2117; rows from the bottom up, pixels left to right; run to completion, no time slicing).  The GPU
         // build has evaluated every pixel: take away what the reference had not reached, recount the display flags, and
         // report the error with that table in place.  (A stripe context knows only its own rows: bk_multi_build / the host
         // of a bk_comm group hands every stripe the group's first failing pixel - bk_truncate_build.)
-        ctx->last_bad_key = std::max((unsigned int)flags[BK_MAX_PLATES + 2], host_bad_key);
+        ctx->last_bad_key = (unsigned int)counters[BK_MAX_PLATES + 2];
         int disp[BK_MAX_PLATES];
         if (int r = bk::launch_truncate_scan(ctx, ctx->last_bad_key, disp)) return r;
         for (int i = 0; i < BK_MAX_PLATES; ++i) { ctx->display[i] = i < ctx->numplates ? disp[i] : 0; if (display_out) display_out[i] = ctx->display[i]; }
@@ -2327,12 +2321,13 @@ extern "C" int bk_debug_host_entries(bk_ctx *ctx, const uint32_t *ids, size_t n,
     for (size_t i = 0; i < n; ++i) if (ids[i] >= px) return ctx->fail(BK_E_INVALID, "bk_debug_host_entries: index out of range");
     std::vector<int> shown(n), err(n, 0);
     try {
-        std::string src;
-        HostModuleP hm;
-        if (bk::g_debug.host_module != 2 && generate_source(ctx, P, &src) == BK_OK) hm = fixup_module(P, src);
-        if (bk::g_debug.host_module == 1 && !hm) return ctx->fail(BK_E_STATE, "bk_debug_host_entries: no host module (no C++ compiler, or host math is not the platform libm)");
-        if (hm) hostmod_runs(n, [&](size_t i0, size_t cnt) { hm->inverse(&bp, &ids[i0], 1, (unsigned long)cnt, &offsets[i0], &tints[i0], &shown[i0], &err[i0]); });
-        else for_each_flagged(P, n, [&](HostEval &E, size_t i) { h_inverse_entry(E, bp, ids[i], &offsets[i], &tints[i], &shown[i], &err[i]); });
+        std::string src;                                  // (none: the interpreter answers)
+        if (bk::g_debug.host_module != 2 && generate_source(ctx, P, &src) != BK_OK) src.clear();
+        if (bk::g_debug.host_module == 1 && (src.empty() || !fixup_module(P, src)))
+            return ctx->fail(BK_E_STATE, "bk_debug_host_entries: no host module (no C++ compiler, or host math is not the platform libm)");
+        rederive(ctx, P, src, ids, 1, n, false,
+                 [&](const HostModule &hm, const uint32_t *id, int stride, unsigned long cnt, size_t i) { hm.inverse(&bp, id, stride, cnt, &offsets[i], &tints[i], &shown[i], &err[i]); },
+                 [&](HostEval &E, uint32_t id, size_t i) { h_inverse_entry(E, bp, id, &offsets[i], &tints[i], &shown[i], &err[i]); });
     } catch (const LuaError &e) {
         return ctx->fail(BK_E_SCRIPT, "%s", e.what());
     }
@@ -2362,12 +2357,13 @@ extern "C" int bk_debug_host_corners(bk_ctx *ctx, const uint32_t *ids, size_t n,
     for (size_t i = 0; i < n; ++i) if (ids[i] >= total) return ctx->fail(BK_E_INVALID, "bk_debug_host_corners: index out of range");
     std::vector<int> err(n, 0), x(n), y(n);
     try {
-        std::string src;
-        HostModuleP hm;
-        if (bk::g_debug.host_module != 2 && generate_source(ctx, P, &src) == BK_OK) hm = fixup_module(P, src);
-        if (bk::g_debug.host_module == 1 && !hm) return ctx->fail(BK_E_STATE, "bk_debug_host_corners: no host module (no C++ compiler, or host math is not the platform libm)");
-        if (hm) hostmod_runs(n, [&](size_t i0, size_t cnt) { hm->corners(&bp, &ids[i0], 1, (unsigned long)cnt, &x[i0], &y[i0], &ok[i0], &err[i0]); });
-        else for_each_flagged(P, n, [&](HostEval &E, size_t i) { h_corner_entry(ctx, E, bp, ids[i], &x[i], &y[i], &ok[i], &err[i]); });
+        std::string src;                                  // (none: the interpreter answers)
+        if (bk::g_debug.host_module != 2 && generate_source(ctx, P, &src) != BK_OK) src.clear();
+        if (bk::g_debug.host_module == 1 && (src.empty() || !fixup_module(P, src)))
+            return ctx->fail(BK_E_STATE, "bk_debug_host_corners: no host module (no C++ compiler, or host math is not the platform libm)");
+        rederive(ctx, P, src, ids, 1, n, false,
+                 [&](const HostModule &hm, const uint32_t *id, int stride, unsigned long cnt, size_t i) { hm.corners(&bp, id, stride, cnt, &x[i], &y[i], &ok[i], &err[i]); },
+                 [&](HostEval &E, uint32_t id, size_t i) { h_corner_entry(ctx, E, bp, id, &x[i], &y[i], &ok[i], &err[i]); });
     } catch (const LuaError &e) {
         return ctx->fail(BK_E_SCRIPT, "%s", e.what());
     }
@@ -2449,38 +2445,24 @@ extern "C" int bk_save_plate(bk_ctx *ctx, int frame, int plate, int with_margins
     if (int r = compile_module(ctx, P, src)) return r;
     hipFunction_t fn = nullptr;
     BK_HIP(ctx, hipModuleGetFunction(&fn, P->module, "bk_save_plate"));
-    if (!ctx->d_flag_list) {
-        BK_HIP(ctx, hipMalloc((void **)&ctx->d_flag_list, (size_t)65536 * 4 * sizeof(uint32_t)));
-        ctx->flag_cap = 65536;
-    }
+    if (int r = alloc_flag_buffers(ctx)) return r;
     const uint8_t *globe = ctx->d_globe + (size_t)frame * ctx->globe_stride();
     uint8_t *out = nullptr;
     BK_HIP(ctx, hipMalloc((void **)&out, (size_t)ctx->ps * ctx->ps));
+    const DeviceMem out_mem(out);
+    BkBuildParams bp;
+    fill_params(ctx, &bp);
+    void *args[] = {&bp, &plate, &with_margins, &globe, &out};
+    int counters[kNumCounters];
     std::vector<uint32_t> flagged;
-    hipError_t e = hipSuccess;
-    for (;;) {
-        BkBuildParams bp;
-        fill_params(ctx, &bp);
-        void *args[] = {&bp, &plate, &with_margins, &globe, &out};
-        int counters[BK_MAX_PLATES + 2];
-        e = hipMemsetAsync(ctx->d_display, 0, sizeof counters, ctx->stream);
-        if (e == hipSuccess) e = hipModuleLaunchKernel(fn, (unsigned)((ctx->ps + 255) / 256), (unsigned)ctx->ps, 1, 256, 1, 1, 0, ctx->stream, args, nullptr);
-        if (e == hipSuccess) e = hipMemcpyAsync(counters, ctx->d_display, sizeof counters, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) break;
-        bool retry = false;
-        if (int r = read_flagged(ctx, (unsigned)counters[BK_MAX_PLATES + 1], &flagged, &retry)) { (void)hipFree(out); return r; }
-        if (!retry) break;
-    }
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(dst_host, (size_t)dst_pitch, out, (size_t)ctx->ps, (size_t)ctx->ps, (size_t)ctx->ps, hipMemcpyDeviceToHost, ctx->stream);
+    if (int r = flagged_pass(ctx, "bk_save_plate", bp, true, [&] {
+            return hipModuleLaunchKernel(fn, (unsigned)((ctx->ps + 255) / 256), (unsigned)ctx->ps, 1, 256, 1, 1, 0, ctx->stream, args, nullptr);
+        }, counters, &flagged)) return r;
+    hipError_t e = hipMemcpy2DAsync(dst_host, (size_t)dst_pitch, out, (size_t)ctx->ps, (size_t)ctx->ps, (size_t)ctx->ps, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(out);
     if (e != hipSuccess) return ctx->fail(BK_E_HIP, "bk_save_plate failed: %s", hipGetErrorString(e));
     // texels whose plate ownership a globe_plate script decides on libm's last bits: the host interpreter has the say
     if (!flagged.empty()) {
-        BkBuildParams bp;
-        fill_params(ctx, &bp);
         const size_t nfl = flagged.size() / 4;
         std::vector<uint8_t> own(nfl);
         try {
