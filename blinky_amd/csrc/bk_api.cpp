@@ -152,6 +152,7 @@ extern "C" void bk_destroy(bk_ctx *ctx)
     free_plate_slots(ctx);
     hipFree(ctx->d_globe);
     hipFree(ctx->d_plate_stage);
+    hipFree(ctx->d_rgba_stage);
     hipFree(ctx->d_pal);
     hipFree(ctx->d_display);
     hipFree(ctx->d_flag_list);
@@ -228,6 +229,7 @@ void bk::empty_context(bk_ctx *ctx)
     free_maps(ctx);
     (void)hipFree(ctx->d_globe); ctx->d_globe = nullptr; ctx->globe_bytes = 0;
     (void)hipFree(ctx->d_plate_stage); ctx->d_plate_stage = nullptr;
+    (void)hipFree(ctx->d_rgba_stage); ctx->d_rgba_stage = nullptr; ctx->rgba_stage_bytes = 0;
     ctx->W = ctx->H = ctx->ps = ctx->gp = ctx->ph = 0;
     ctx->row0 = ctx->row1 = 0;
     ctx->lensmap_valid = false;
@@ -562,6 +564,51 @@ extern "C" int bk_upload_plate_async(bk_ctx *ctx, int frame, int plate, const ui
     return BK_OK;
 }
 
+// ---- truecolour plates: globe g = ring slots 4g .. 4g+3, slot 4g+c holds byte c of every texel ---------------------------------
+static int rgba_plate_args(bk_ctx *ctx, const char *who, int globe, int plate, int src_pitch)
+{
+    if (ctx->device < 0) return ctx->fail(BK_E_STATE, "%s: this context was created without a device (BK_DEVICE_NONE)", who);
+    if (!ctx->d_globe) return ctx->fail(BK_E_STATE, "%s: call bk_resize first", who);
+    if (plate < 0 || plate >= BK_MAX_PLATES || globe < 0 || globe >= ctx->nframes / 4 || src_pitch < 4 * ctx->ps)
+        return ctx->fail(BK_E_INVALID, "%s: bad globe/plate/pitch (%d truecolour globes resident: bk_set_frames(4 * globes))", who, ctx->nframes / 4);
+    return BK_OK;
+}
+
+extern "C" int bk_upload_plate_rgba_device(bk_ctx *ctx, int globe, int plate, const void *src_dev, int src_pitch)
+{
+    if (!ctx || !src_dev) return BK_E_INVALID;
+    if (int r = rgba_plate_args(ctx, "bk_upload_plate_rgba_device", globe, plate, src_pitch)) return r;
+    if (int r = ensure_device(ctx)) return r;
+    bk::Range range("bk_upload_plate_rgba_device");
+    uint8_t *plane0 = ctx->d_globe + (size_t)(4 * globe) * ctx->globe_stride() + (size_t)plate * ctx->plate_bytes();
+    return bk::launch_plate_rgba_retile(ctx, plane0, (const uint8_t *)src_dev, (size_t)src_pitch);
+}
+
+extern "C" int bk_upload_plate_rgba(bk_ctx *ctx, int globe, int plate, const uint8_t *src, int src_pitch)
+{
+    if (!ctx || !src) return BK_E_INVALID;
+    if (int r = rgba_plate_args(ctx, "bk_upload_plate_rgba", globe, plate, src_pitch)) return r;
+    if (int r = ensure_device(ctx)) return r;
+    bk::Range range("bk_upload_plate_rgba");
+    const size_t ps = ctx->ps, row = 4 * ps, bytes = row * ps;
+    if (ctx->rgba_stage_bytes != bytes) {                    // (first use, or the platesize has changed since)
+        BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipFree(ctx->d_rgba_stage);
+        ctx->d_rgba_stage = nullptr;
+        ctx->rgba_stage_bytes = 0;
+        if (hipMalloc((void **)&ctx->d_rgba_stage, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return ctx->fail(BK_E_NOMEM, "bk_upload_plate_rgba: out of device memory (plate staging, %zu bytes)", bytes);
+        }
+        ctx->rgba_stage_bytes = bytes;
+    }
+    BK_HIP(ctx, hipMemcpy2DAsync(ctx->d_rgba_stage, row, src, (size_t)src_pitch, row, ps, hipMemcpyHostToDevice, ctx->stream));
+    uint8_t *plane0 = ctx->d_globe + (size_t)(4 * globe) * ctx->globe_stride() + (size_t)plate * ctx->plate_bytes();
+    if (int r = bk::launch_plate_rgba_retile(ctx, plane0, ctx->d_rgba_stage, row)) return r;
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BK_OK;
+}
+
 extern "C" int bk_download_plate(bk_ctx *ctx, int frame, int plate, uint8_t *dst_host, int dst_pitch)
 {
     if (!ctx || !dst_host) return BK_E_INVALID;
@@ -643,6 +690,24 @@ extern "C" int bk_apply_device(bk_ctx *ctx, int frame0, int nframes, void *dst_d
     if (int r = upload_pal(ctx, rubix_on, pal)) return r;
     uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + x0;
     return bk::launch_apply(ctx, frame0, nframes, first, dst_pitch, frame_stride, rubix_on);
+}
+
+// truecolour frames: frame f from truecolour globe (globe0 + f) % (ring slots / 4), 4 bytes per pixel (bk_apply_rgba.inc)
+extern "C" int bk_apply_rgba_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch, size_t frame_stride, int x0, int y0)
+{
+    if (!ctx || !dst_dev) return BK_E_INVALID;
+    if (ctx->device < 0) return ctx->fail(BK_E_STATE, "bk_apply_rgba_device: this context was created without a device (BK_DEVICE_NONE)");
+    if (!ctx->lensmap_valid) return ctx->fail(BK_E_STATE, "bk_apply_rgba_device: no lensmap (bk_build / bk_set_lensmap first)");
+    if (x0 < 0 || y0 < 0 || globe0 < 0 || nframes < 1 || (long long)dst_pitch < 4ll * ((long long)ctx->W + x0))
+        return ctx->fail(BK_E_INVALID, "bk_apply_rgba_device: bad pitch/origin/frames");
+    if (((uintptr_t)dst_dev | (uintptr_t)dst_pitch | (uintptr_t)frame_stride) & 3u)
+        return ctx->fail(BK_E_INVALID, "bk_apply_rgba_device: dst, pitch and frame stride must be multiples of 4 bytes");
+    if (ctx->nframes < 4) return ctx->fail(BK_E_STATE, "bk_apply_rgba_device: a truecolour globe is four ring slots (bk_set_frames(4 * globes))");
+    if (ctx->apply_variant == 0) return ctx->fail(BK_E_STATE, "bk_apply_rgba_device: the truecolour apply is the staged variant (bk_set_apply_variant 2 / -1)");
+    if (int r = ensure_device(ctx)) return r;                // (ends a resident session, as bk_apply_device)
+    bk::Range range("bk_apply_rgba_device");
+    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
+    return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride);
 }
 
 // ---- resident single-frame apply (bk_apply_resident.inc) ------------------------------------------------------------

@@ -177,6 +177,47 @@ __global__ __launch_bounds__(256) void plate_retile_kernel(uint8_t *__restrict__
     if (to_tiled) *t = *r; else *r = *t;
 }
 
+// one TRUECOLOUR plate - row-major, ps rows of ps 32-bit texels, rows src_pitch bytes apart - into the same plate of four consecutive
+// globe slots (plane_stride bytes apart): byte c of every texel goes to slot c, in the tiled layout every slot has.  A thread reads the
+// 64 contiguous bytes of 16 texels of a row and writes one 16-byte chunk into each plane (the texels past ps of a row's last chunk as
+// zeros: padding nothing reads).  wide: src and src_pitch are multiples of 16 (vector loads); else multiples of 4 (dword loads) or
+// of nothing (align1: byte loads).
+__global__ __launch_bounds__(256) void plate_rgba_retile_kernel(uint8_t *__restrict__ plane0, size_t plane_stride, const uint8_t *__restrict__ src,
+                                                                size_t src_pitch, int ps, int gp, int ph, int wide, int align1)
+{
+    const int cpr = (ps + 15) >> 4;
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= cpr * ps) return;
+    const int py = id / cpr, cx = id - py * cpr;
+    const int cnt = min(16, ps - cx * 16);                  // texels of this chunk inside the plate
+    const uint8_t *s = src + (size_t)py * src_pitch + (size_t)cx * 64;
+    uint32_t t[16];                                          // the 16 texels
+    if (cnt == 16 && wide) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint4 q = reinterpret_cast<const uint4 *>(s)[j];
+            t[4 * j] = q.x; t[4 * j + 1] = q.y; t[4 * j + 2] = q.z; t[4 * j + 3] = q.w;
+        }
+    } else if (!align1) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t[k] = k < cnt ? reinterpret_cast<const uint32_t *>(s)[k] : 0u;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            t[k] = k < cnt ? (uint32_t)s[4 * k] | ((uint32_t)s[4 * k + 1] << 8) | ((uint32_t)s[4 * k + 2] << 16) | ((uint32_t)s[4 * k + 3] << 24) : 0u;
+    }
+    uint8_t *out = plane0 + bk_texel_offset((uint32_t)gp, (uint32_t)ph, 0u, (uint32_t)cx * 16u, (uint32_t)py);   // 16-byte aligned
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            w[j] = ((t[4 * j] >> (8 * c)) & 0xFFu) | (((t[4 * j + 1] >> (8 * c)) & 0xFFu) << 8) | (((t[4 * j + 2] >> (8 * c)) & 0xFFu) << 16) |
+                   (((t[4 * j + 3] >> (8 * c)) & 0xFFu) << 24);
+        *reinterpret_cast<uint4 *>(out + (size_t)c * plane_stride) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
 // sparse patches of a device table (the handful of lensmap entries / texel corners the host re-derives on the
 // platform libm after a build, bk_lens.cpp): dst[idx[i]] = val[i]
 template <typename T>
@@ -291,6 +332,16 @@ int launch_plate_retile(bk_ctx *ctx, uint8_t *plate_tiled, int to_tiled, uint8_t
     const int threads = (ctx->gp >> 4) * ctx->ps;
     hipLaunchKernelGGL(plate_retile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
                        plate_tiled, rowmajor ? rowmajor : ctx->d_plate_stage, ctx->ps, ctx->gp, ctx->ph, to_tiled);
+    BK_HIP(ctx, hipGetLastError());
+    return BK_OK;
+}
+
+int launch_plate_rgba_retile(bk_ctx *ctx, uint8_t *plane0, const uint8_t *src_dev, size_t src_pitch)
+{
+    const int threads = ((ctx->ps + 15) >> 4) * ctx->ps;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src_dev) | (uintptr_t)src_pitch;
+    hipLaunchKernelGGL(plate_rgba_retile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, plane0, ctx->globe_stride(),
+                       src_dev, src_pitch, ctx->ps, ctx->gp, ctx->ph, (a & 15) == 0 ? 1 : 0, (a & 3) != 0 ? 1 : 0);
     BK_HIP(ctx, hipGetLastError());
     return BK_OK;
 }

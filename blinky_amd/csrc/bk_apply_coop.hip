@@ -1353,24 +1353,37 @@ int launch_apply_coop(bk_ctx *ctx, int frame0, int nframes, uint8_t *dst, int ds
     return launch_compiled(ctx, ctx->coopmap, frame0, nframes, dst, dst_pitch, frame_stride, rubix_on);
 }
 
+// What every launch over a compiled block map decides the same way (the 8-bit launch below, the truecolour one in bk_apply_rgba.inc).
+// Frames per block visit of a launch of `nframes` 8-bit frames: 8, but a batch of 8..15 frames is split in two groups so that the grid
+// has more workgroups than one scheduling round holds (8 frames: 3.86 -> 3.70 us/frame)
+static int coop_frames_per_visit(const bk_ctx *ctx, const CoopMap *cm, int nframes)
+{
+    int fmax = ctx->apply_fchunk > 0 ? ctx->apply_fchunk : cm->fchunk > 0 ? cm->fchunk : 8;
+    if (ctx->apply_fchunk <= 0 && cm->fchunk <= 0 && nframes >= 8 && nframes < 16) fmax = (nframes + 1) / 2;
+    return nframes < fmax ? nframes : fmax;
+}
+// The staging buffer of the launch.  The block map's statistics are folded in FIRST if they have arrived: coop_stats_wait may enlarge
+// cm->lds_bytes (the exact histogram can show a block the strided survey missed), and the dynamic-LDS size of the launch, the
+// staging-buffer size the kernel is told and the palette's place behind it must all come from the same value.
+static int coop_launch_lds(bk_ctx *ctx, CoopMap *cm)
+{
+    if (cm->stats_pending && hipEventQuery(cm->stats_ready) == hipSuccess) (void)coop_stats_wait(ctx, cm);
+    return cm->lds_bytes;
+}
+// one-block-per-workgroup grids: take the cost-balanced workgroup -> block map if bands of equal block count are known to be uneven
+// (the block map's statistics arrive asynchronously: until they are here, the direct mapping)
+static bool coop_wants_wgmap(const CoopMap *cm, int kflags) { return !(kflags & (16 | 64)) && !cm->stats_pending && cm->stats[7]; }
+
 // the apply launch over an already compiled block map
 static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, uint8_t *dst, int dst_pitch, size_t frame_stride, int rubix_on)
 {
     const int rows = ctx->rows();
     const int blocks_x = cm->blocks_x, nblocks = blocks_x * cm->blocks_y;
     if ((rubix_on != 0) != cm->tinted) return ctx->fail(BK_E_STATE, "apply: the block map is not of this launch's flavour (internal)");
-    // frames per block visit: 8, but a batch of 8..15 frames is split in two groups so that the grid has more
-    // workgroups than one scheduling round holds (8 frames: 3.86 -> 3.70 us/frame)
-    int fmax = ctx->apply_fchunk > 0 ? ctx->apply_fchunk : cm->fchunk > 0 ? cm->fchunk : 8;
-    if (ctx->apply_fchunk <= 0 && cm->fchunk <= 0 && nframes >= 8 && nframes < 16) fmax = (nframes + 1) / 2;
-    const int fchunk = nframes < fmax ? nframes : fmax;
+    const int fchunk = coop_frames_per_visit(ctx, cm, nframes);
     const int fblocks = (nframes + fchunk - 1) / fchunk;
     const int per = (nblocks + 7) / 8;
-    // Fold the block map's statistics in FIRST if they have arrived: coop_stats_wait may enlarge cm->lds_bytes (the exact
-    // histogram can show a block the strided survey missed), and the dynamic-LDS size of the launch, the staging-buffer
-    // size the kernel is told and the palette's place behind it must all come from the same value.
-    if (cm->stats_pending && hipEventQuery(cm->stats_ready) == hipSuccess) (void)coop_stats_wait(ctx, cm);
-    const int lds_buf = cm->lds_bytes;
+    const int lds_buf = coop_launch_lds(ctx, cm);
     const size_t shmem = (size_t)lds_buf + (rubix_on ? BK_PAL_BYTES : 0);
     // Grid.  One block per workgroup (the finest split, dealt to the CUs by the hardware as they free up) when that many
     // workgroups are about what the chip holds - `apply_wgs_per_cu` = 16 per CU, deliberately generous: 4K panini x16 runs
@@ -1405,10 +1418,8 @@ static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, ui
     if (wgs_per_band > per) wgs_per_band = per;
     dim3 grid((unsigned)(wgs_per_band * 8), (unsigned)fblocks);
     const bool once = wgs_per_band == per && !(ctx->apply_flags & 32);     // every workgroup has exactly one block (ablation bit 32: persistent form anyway)
-    // one-block form: take the cost-balanced workgroup -> block map if bands of equal block count are known to be uneven
-    // (the block map's statistics arrive asynchronously: until they are here, the direct mapping)
     int kflags = ctx->apply_flags & ~BK_KF_WGMAP;
-    if (once && !(kflags & (16 | 64)) && !cm->stats_pending && cm->stats[7]) kflags |= BK_KF_WGMAP;
+    if (once && coop_wants_wgmap(cm, kflags)) kflags |= BK_KF_WGMAP;
     // Single-frame launches fetch the globe chunks non-temporally: between two of them it is the block map L2 should keep
     // (4K hammer 12.4 -> 11.6 us, quincuncial 12.8 -> 11.8, panini 8.4 -> 8.2); batch launches lose 3-10 % that way.
     // LDS-DMA staging (bit 256) measured neutral (panini 8.39 -> 8.26, hammer 12.42 -> 12.41): the launch is bound by what
@@ -1600,6 +1611,7 @@ int coopmap_stats(bk_ctx *ctx, int out[6])
     return BK_OK;
 }
 
+#include "bk_apply_rgba.inc"
 #include "bk_apply_resident.inc"
 
 }  // namespace bk

@@ -1,0 +1,246 @@
+// bk_apply_rgba.inc -- part of bk_apply_coop.hip: the TRUECOLOUR apply (bk_apply_rgba_device) for gfx950.
+//
+// A 32-bit globe is four byte planes in four consecutive slots of the globe ring: truecolour globe g = slots 4g .. 4g+3, slot 4g+c
+// holds byte c of every texel in the 16x8-tile layout every other slot has (bk_texel_offset).  The lensmap, the block map - chunk
+// lists, 16-bit LDS addresses, walk order, XCD bands - are therefore valid as they are for every plane, and a truecolour frame is
+// four of the 8-bit gathers through the same block map: per plane the block's chunks are staged to LDS and gathered into four more
+// accumulator bytes per pixel; after the fourth plane a lane's 4x4 bytes are transposed in registers (v_perm_b32) and leave as whole
+// 32-bit pixels.  The bytes are opaque: RGBA, BGRA, any 4-byte texel warps the same way.
+//
+// Which pixels a lane takes: its ROW is the one coop_compile_kernel gives it, but of the row's 32 four-pixel groups (16 bytes of frame
+// each) lane j of the row's 32/RG takes groups j, j + 32/RG, j + 2 * 32/RG ... instead of RG consecutive ones - it simply loads those
+// groups' LDS addresses from the block map (rgba_load_idx) - so that store instruction r of a wave writes the contiguous 16-byte
+// pieces r * 32/RG + j: whole 128-byte lines per instruction, as the 8-bit kernel's one store per lane does
+// (16 truecolour frames of 4K panini take 224.6 us, the 64 8-bit frames of the same slots 224.4; hammer 426.0 / 431.5:
+//  profiles/rgba_apply.txt, which also has what consecutive pixels per lane cost).
+// One block per workgroup, the PLAIN block map as ensure_coopmap compiles and tunes it for a launch of 4 * nframes planes; a block
+// visit serves max(1, fchunk / 4) truecolour frames, i.e. the block map is read once per about 8 planes as in the 8-bit batch
+// launch.  No rubix, no strided / persistent / LDS-DMA form.
+// Blocks the staging does not serve - a chunk list larger than the launch's staging buffer, CF_SLOW blocks without a list - gather
+// straight from the lensmap: four byte loads and one dword store per mapped pixel (rare on real lenses; no multi-pass form).
+
+// the lane's 4 pixels of row group r as whole dwords: P[c] holds byte c of pixels 0..3 -> px[k] holds bytes 0..3 of pixel k
+__device__ __forceinline__ void bk_rgba_transpose(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t px[4])
+{
+    // v_perm_b32 D = perm(S0, S1, sel): selector byte 0-3 picks that byte of S1, 4-7 byte (n - 4) of S0
+    const uint32_t t0 = __builtin_amdgcn_perm(p1, p0, 0x05010400u);      // p0.b0 p1.b0 p0.b1 p1.b1
+    const uint32_t t1 = __builtin_amdgcn_perm(p1, p0, 0x07030602u);      // p0.b2 p1.b2 p0.b3 p1.b3
+    const uint32_t u0 = __builtin_amdgcn_perm(p3, p2, 0x05010400u);
+    const uint32_t u1 = __builtin_amdgcn_perm(p3, p2, 0x07030602u);
+    px[0] = __builtin_amdgcn_perm(u0, t0, 0x05040100u);
+    px[1] = __builtin_amdgcn_perm(u0, t0, 0x07060302u);
+    px[2] = __builtin_amdgcn_perm(u1, t1, 0x05040100u);
+    px[3] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
+}
+
+// truecolour frames of one staged block: four planes per frame through the one staging buffer, plane c + 1's chunks requested before
+// plane c's gather (coop_frames does the same from frame to frame)
+template <int NQ, int RG>
+__device__ __forceinline__ void rgba_frames(const uint8_t *__restrict__ globe, size_t globe_stride, int tglobes, int globe0, int f_begin,
+                                            int f_end, uint8_t *__restrict__ dst, int dst_pitch, size_t frame_stride, uint8_t *buf,
+                                            const uint32_t *__restrict__ blist, uint32_t nchunks, uint32_t s0, uint32_t s1, uint32_t s2,
+                                            uint32_t s3, bool k0, bool k1, bool k2, bool k3, const CoopIdx<RG> ix, bool fast_store,
+                                            bool tile_empty, int row0, int xb, int cx)
+{
+    // ix.iw[r] = the LDS addresses of the row's four-pixel group r * LPR + cx (rgba_load_idx); xb = the block's first pixel column
+    constexpr int LPR = 32 / RG;
+    uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0, q2 = q0, q3 = q0;      // (scalars, not an array: they must stay in VGPRs)
+#define BK_RGBA_PLANE(F, C) (globe + (size_t)(4 * ((globe0 + (F)) % tglobes) + (C)) * globe_stride)
+#define BK_RGBA_LOADS(F, C)                                                                    \
+    do {                                                                                       \
+        const uint8_t *gl_ = BK_RGBA_PLANE(F, C);                                              \
+        q0 = *reinterpret_cast<const uint4 *>(gl_ + s0);                                       \
+        if (NQ > 1) q1 = *reinterpret_cast<const uint4 *>(gl_ + s1);                           \
+        if (NQ > 2) q2 = *reinterpret_cast<const uint4 *>(gl_ + s2);                           \
+        if (NQ > 3) q3 = *reinterpret_cast<const uint4 *>(gl_ + s3);                           \
+    } while (0)
+#define BK_RGBA_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")      /* LDS traffic only: BK_LDS_BARRIER */
+    uint8_t *mine = buf + threadIdx.x * 16u;
+    if (f_begin < f_end) BK_RGBA_LOADS(f_begin, 0);
+    for (int f = f_begin; f < f_end; ++f) {
+        uint32_t acc[4][RG];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (k0) *reinterpret_cast<uint4 *>(mine) = q0;
+            if (NQ > 1 && k1) *reinterpret_cast<uint4 *>(mine + 4096) = q1;
+            if (NQ > 2 && k2) *reinterpret_cast<uint4 *>(mine + 8192) = q2;
+            if (NQ > 3 && k3) *reinterpret_cast<uint4 *>(mine + 12288) = q3;
+            if (NQ == 4) {
+                const uint8_t *gl = BK_RGBA_PLANE(f, c);
+                for (uint32_t c0 = 1024; c0 < nchunks; c0 += 1024) {      // blocks above what the registers hold: rounds of four loads
+                    const uint32_t n = c0 + threadIdx.x;
+                    const bool m0 = n < nchunks, m1 = n + 256u < nchunks, m2 = n + 512u < nchunks, m3 = n + 768u < nchunks;
+                    const uint32_t a0 = m0 ? blist[n] : 0u, a1 = m1 ? blist[n + 256u] : 0u, a2 = m2 ? blist[n + 512u] : 0u,
+                                   a3 = m3 ? blist[n + 768u] : 0u;
+                    q0 = *reinterpret_cast<const uint4 *>(gl + a0);
+                    q1 = *reinterpret_cast<const uint4 *>(gl + a1);
+                    q2 = *reinterpret_cast<const uint4 *>(gl + a2);
+                    q3 = *reinterpret_cast<const uint4 *>(gl + a3);
+                    uint8_t *md = mine + (size_t)c0 * 16u;
+                    if (m0) *reinterpret_cast<uint4 *>(md) = q0;
+                    if (m1) *reinterpret_cast<uint4 *>(md + 4096) = q1;
+                    if (m2) *reinterpret_cast<uint4 *>(md + 8192) = q2;
+                    if (m3) *reinterpret_cast<uint4 *>(md + 12288) = q3;
+                }
+            }
+            BK_RGBA_BARRIER();                // the plane's chunks are in `buf`
+            if (c < 3) BK_RGBA_LOADS(f, c + 1);
+            else if (f + 1 < f_end) BK_RGBA_LOADS(f + 1, 0);
+            if (!tile_empty) {
+#pragma unroll
+                for (int r = 0; r < RG; ++r) {
+                    const uint32_t a[4] = {ix.iw[r].x & 0xFFFFu, ix.iw[r].x >> 16, ix.iw[r].y & 0xFFFFu, ix.iw[r].y >> 16};
+                    uint32_t v[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[k] = (fast_store || a[k] != 0xFFFFu) ? buf[a[k]] : 0u;
+                    acc[c][r] = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+                }
+                if (c == 3) {
+                    uint8_t *out = dst + (size_t)f * frame_stride + (size_t)row0 * dst_pitch + (size_t)xb * 4 + (size_t)cx * 16;
+#pragma unroll
+                    for (int r = 0; r < RG; ++r) {
+                        uint32_t px[4];
+                        bk_rgba_transpose(acc[0][r], acc[1][r], acc[2][r], acc[3][r], px);
+                        if (fast_store) {
+                            // non-temporal, as the 8-bit frames: never read back here, L2 stays with the globe lines blocks share
+                            typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+                            v4u v = {px[0], px[1], px[2], px[3]};
+                            __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(out + 16 * LPR * r));
+                        } else {
+                            const uint32_t a[4] = {ix.iw[r].x & 0xFFFFu, ix.iw[r].x >> 16, ix.iw[r].y & 0xFFFFu, ix.iw[r].y >> 16};
+#pragma unroll
+                            for (int k = 0; k < 4; ++k)
+                                if (a[k] != 0xFFFFu) reinterpret_cast<uint32_t *>(out + 16 * LPR * r)[k] = px[k];
+                        }
+                    }
+                }
+            }
+            BK_RGBA_BARRIER();                // every wave is done with `buf`
+        }
+    }
+#undef BK_RGBA_BARRIER
+#undef BK_RGBA_LOADS
+#undef BK_RGBA_PLANE
+}
+
+// the LDS addresses of the four-pixel groups this lane takes: group g = r * LPR + cx of its row, which the block map files under lane
+// (row's first lane + g / RG), row group g % RG ([blk][wave][RG][64 lanes][4] u16)
+template <int RG>
+__device__ __forceinline__ CoopIdx<RG> rgba_load_idx(const uint16_t *__restrict__ idx, int blk, int wave, int lane)
+{
+    constexpr int LPR = 32 / RG;
+    const int first = lane - lane % LPR, cx = lane % LPR;
+    CoopIdx<RG> ix;
+#pragma unroll
+    for (int r = 0; r < RG; ++r) {
+        const int g = r * LPR + cx;
+        const size_t slab = (((size_t)blk * 4 + wave) * RG + g % RG) * 256 + (size_t)(first + g / RG) * 4;
+        ix.iw[r] = *reinterpret_cast<const uint2 *>(idx + slab);
+    }
+    return ix;
+}
+
+// truecolour frames of a block the staging does not serve: straight from the lensmap, pixel by pixel
+template <int RG>
+__device__ __forceinline__ void rgba_direct_frames(const uint32_t *__restrict__ lmap, const uint8_t *__restrict__ globe, size_t globe_stride,
+                                                   int tglobes, int globe0, int f_begin, int f_end, uint8_t *__restrict__ dst, int dst_pitch,
+                                                   size_t frame_stride, int W, int rows, int row0, int x)
+{
+    if (row0 >= rows) return;
+    for (int f = f_begin; f < f_end; ++f) {
+        const uint8_t *p0 = globe + (size_t)(4 * ((globe0 + f) % tglobes)) * globe_stride;
+        uint32_t *out = reinterpret_cast<uint32_t *>(dst + (size_t)f * frame_stride + (size_t)row0 * dst_pitch + (size_t)x * 4);
+        for (int i = 0; i < 4 * RG; ++i) {
+            if (x + i >= W) break;
+            const uint32_t o = lmap[(size_t)row0 * W + x + i];
+            if (o == BK_NULL_OFFSET) continue;
+            out[i] = (uint32_t)p0[o] | ((uint32_t)p0[globe_stride + o] << 8) | ((uint32_t)p0[2 * globe_stride + o] << 16) |
+                     ((uint32_t)p0[3 * globe_stride + o] << 24);
+        }
+    }
+}
+
+// globe_frames = TRUECOLOUR globes resident (ring slots / 4), frame0 = the first one, nframes / fchunk in truecolour frames; dst =
+// pixel (0, first owned row), 4 bytes per pixel.  tint_t, pal, order, bands: unused (BK_COOP_KERNEL_ARGS is the launchers' one list).
+// (no amdgpu_waves_per_eu: the twelve more accumulator dwords than the 8-bit one-block form put RG = 4 at 77 VGPRs = 6 waves per SIMD;
+//  asking for 8 would spill them, and at RG = 4 the staging buffer - 18 KiB and more on real lenses - allows 8 workgroups per CU at best)
+template <int RG>
+__global__ __launch_bounds__(256) void apply_coop_rgba_kernel(BK_COOP_KERNEL_ARGS)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    (void)tint_t; (void)pal; (void)order; (void)bands;
+    constexpr int N = 1024 * RG;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int blk;
+    if (kflags & BK_KF_WGMAP) {                       // bands of equal cost, as apply_coop_once_kernel
+        const uint32_t m = wgmap[blockIdx.x];
+        if (m == 0xFFFFFFFFu) return;
+        blk = (int)m;
+    } else {
+        const int per = (nblocks + 7) / 8, band = (int)(blockIdx.x & 7);
+        const int l = band * per + (int)(blockIdx.x >> 3);
+        if (l >= min(nblocks, (band + 1) * per)) return;
+        blk = bk_block_at(l, blocks_x, nblocks, kflags);
+    }
+    const int f_begin = blockIdx.y * fchunk, f_end = min(nframes, f_begin + fchunk);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dst_pitch | (uintptr_t)frame_stride) & (uintptr_t)15) == 0;
+    constexpr int LPR = 32 / RG;                      // a lane's row as in coop_compile_kernel; its pixels of that row: see the head comment
+    const int ry = wave * 2 * RG + lane / LPR, cx = lane % LPR;
+    const CoopPrefetch<RG> cur = coop_fetch<false, RG>(hdr, list, blk);
+    const uint32_t nchunks = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.h.x);
+    const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.h.y);
+    if (flags & CF_EMPTY) return;
+    const int by = blk / blocks_x, bx = blk - by * blocks_x;
+    // (x: the lane's 4 * RG CONSECUTIVE pixels, coop_compile_kernel's mapping - used by the direct gather below only, which reads
+    //  the lensmap and needs no block-map addresses; the staged path takes the strided groups of the head comment instead)
+    const int row0 = by * 8 * RG + ry, x = bx * 128 + cx * 4 * RG;
+    const bool tile_all = (flags >> wave) & 1u, tile_empty = (flags >> (4 + wave)) & 1u;
+    if ((flags & CF_SLOW) || (int)(nchunks * 16u) > lds_buf) {
+        if (!tile_empty)
+            rgba_direct_frames<RG>(lmap, globe, globe_stride, globe_frames, frame0, f_begin, f_end, dst, dst_pitch, frame_stride, W, rows, row0, x);
+        return;
+    }
+    const CoopIdx<RG> ix = rgba_load_idx<RG>(idx, blk, wave, lane);
+    const bool k0 = threadIdx.x < nchunks, k1 = threadIdx.x + 256u < nchunks, k2 = threadIdx.x + 512u < nchunks, k3 = threadIdx.x + 768u < nchunks;
+    const uint32_t s0 = k0 ? cur.c[0] : 0u, s1 = k1 ? cur.c[1] : 0u, s2 = k2 ? cur.c[2] : 0u, s3 = k3 ? cur.c[3] : 0u;
+    const uint32_t *bl = list + (size_t)blk * N;
+    const bool fast_store = tile_all && aligned;
+    const uint32_t nq = (nchunks + 255u) >> 8;
+#define BK_RGBA(NQ_) rgba_frames<NQ_, RG>(globe, globe_stride, globe_frames, frame0, f_begin, f_end, dst, dst_pitch, frame_stride, smem, bl, nchunks, \
+                                          s0, s1, s2, s3, k0, k1, k2, k3, ix, fast_store, tile_empty, row0, bx * 128, cx)
+    if (nq <= 1) BK_RGBA(1);
+    else if (nq == 2) BK_RGBA(2);
+    else if (nq == 3) BK_RGBA(3);
+    else BK_RGBA(4);
+#undef BK_RGBA
+}
+
+// dst = address of pixel (0, row0) of truecolour frame 0, i.e. the first owned row; globe0 / nframes in truecolour globes / frames
+int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst, int dst_pitch, size_t frame_stride)
+{
+    const int rows = ctx->rows();
+    if (rows <= 0 || nframes <= 0) return BK_OK;
+    const int planes = 4 * nframes;
+    if (int r = ensure_coopmap(ctx, planes, 0)) return r;        // the plain block map, compiled and tuned as for a launch of that many 8-bit frames
+    CoopMap *cm = ctx->coopmap;
+    const int blocks_x = cm->blocks_x, nblocks = blocks_x * cm->blocks_y;
+    // planes per block visit as an 8-bit launch of that many frames has them; a visit serves whole truecolour frames
+    const int fchunk = std::max(1, coop_frames_per_visit(ctx, cm, planes) / 4);
+    const int fblocks = (nframes + fchunk - 1) / fchunk;
+    const int per = (nblocks + 7) / 8;
+    const int lds_buf = coop_launch_lds(ctx, cm);
+    // Of the developer ablations (ctx->apply_flags, bk_debug_set_ablation) this kernel knows one: bit 16, the row-major walk its
+    // bk_block_at call honours.  The others switch parts of the 8-bit kernels this one does not have (forms, DMA staging, the
+    // pipelining, stores off ...) and are deliberately not passed on.
+    int kflags = ctx->apply_flags & 16;
+    if (coop_wants_wgmap(cm, ctx->apply_flags)) kflags |= BK_KF_WGMAP;
+    const dim3 grid((unsigned)(per * 8), (unsigned)fblocks);
+#define BK_APPLY_RGBA(N) hipLaunchKernelGGL((apply_coop_rgba_kernel<N>), grid, dim3(256), (size_t)lds_buf, ctx->stream, cm->d_hdr, cm->d_list, cm->d_idx, \
+                                            ctx->d_tints, ctx->d_offsets, ctx->d_globe, ctx->globe_stride(), ctx->nframes / 4, globe0, dst,       \
+                                            dst_pitch, frame_stride, ctx->W, rows, blocks_x, nblocks, nframes, fchunk, lds_buf,               \
+                                            ctx->d_pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap)
+    if (cm->rg == 1) BK_APPLY_RGBA(1); else if (cm->rg == 2) BK_APPLY_RGBA(2); else BK_APPLY_RGBA(4);
+#undef BK_APPLY_RGBA
+    BK_HIP(ctx, hipGetLastError());
+    return BK_OK;
+}

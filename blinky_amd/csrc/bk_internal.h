@@ -72,6 +72,8 @@ struct bk_ctx {
     // device memory
     uint8_t *d_globe = nullptr;      // [nframes][6][ph/8][gp/16] tiles of 16x8 texels (bk_texel_offset, bk_build_params.h)
     uint8_t *d_plate_stage = nullptr;  // [ps][gp] row-major staging of one plate for bk_upload_plate / bk_download_plate
+    uint8_t *d_rgba_stage = nullptr;   // [ps][4*ps] one truecolour plate on its way from the host (bk_upload_plate_rgba); allocated on first use
+    size_t rgba_stage_bytes = 0;
     // bk_upload_plate_async: pinned host buffers the caller's rows are copied into, their device-side staging twins and
     // the event that says "this slot's DMA + retile are done" - three slots, so that the DMA of plate k overlaps the
     // engine's render of plate k+1
@@ -181,6 +183,9 @@ int launch_mask(bk_ctx *ctx);                 // d_offsets -> d_mask
 int launch_fill_lcg(bk_ctx *ctx, uint8_t *plate_dst, uint32_t seed);   // one plate, padded rows
 int launch_convert_offsets(bk_ctx *ctx, uint32_t *buf, size_t n, int to_device);   // reference <-> device (tiled) layout
 int launch_plate_retile(bk_ctx *ctx, uint8_t *plate_tiled, int to_tiled, uint8_t *rowmajor = nullptr);   // row-major staging (default d_plate_stage) <-> a plate of the globe
+// a row-major plate of 32-bit texels (device memory, rows src_pitch bytes apart) -> the same plate of four consecutive globe slots,
+// byte c of every texel into slot c's tiles; plane0 = the plate in the first of the four slots
+int launch_plate_rgba_retile(bk_ctx *ctx, uint8_t *plane0, const uint8_t *src_dev, size_t src_pitch);
 int launch_scatter32(bk_ctx *ctx, uint32_t *dst, const uint32_t *h_idx, const uint32_t *h_val, size_t n);   // dst[idx[i]] = val[i]; synchronous
 int launch_scatter8(bk_ctx *ctx, uint8_t *dst, const uint32_t *h_idx, const uint8_t *h_val, size_t n);
 // the owned rows of the lensmap as the reference leaves them when its scan stops at the pixel with scan key bad_key - 1 (everything it
@@ -190,6 +195,8 @@ int launch_truncate_scan(bk_ctx *ctx, unsigned int bad_key, int display_out[BK_M
 void coopmap_invalidate(bk_ctx *ctx);
 int launch_apply_coop(bk_ctx *ctx, int frame0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch,
                       size_t frame_stride, int rubix_on);
+// bk_apply_rgba.inc (part of bk_apply_coop.hip): truecolour frames from truecolour globes (four ring slots each)
+int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch, size_t frame_stride);
 int coopmap_stats(bk_ctx *ctx, int out[6]);   // blocks, direct-gather blocks, empty blocks, LDS bytes per buffer
 int coopmap_traffic_model(bk_ctx *ctx, uint64_t out[8]);
 int coopmap_xcd_probe(bk_ctx *ctx, int *out, int nwg);

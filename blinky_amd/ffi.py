@@ -73,6 +73,9 @@ _SIGS = {
     "bk_read_lensmap": (_i, [_vp, _vp, _vp]),
     "bk_upload_plate": (_i, [_vp, _i, _i, _vp, _i]),
     "bk_upload_plate_async": (_i, [_vp, _i, _i, _vp, _i]),
+    "bk_upload_plate_rgba": (_i, [_vp, _i, _i, _vp, _i]),
+    "bk_upload_plate_rgba_device": (_i, [_vp, _i, _i, _vp, _i]),
+    "bk_apply_rgba_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i]),
     "bk_globe_device_ptr": (_vp, [_vp, _i]),
     "bk_fill_plate_lcg": (_i, [_vp, _i, _i, C.c_uint32]),
     "bk_apply": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
@@ -372,6 +375,17 @@ class Context:
         src = np.ascontiguousarray(src, dtype=np.uint8)
         self._chk(lib.bk_upload_plate_async(self._h, frame, plate, _ptr(src), src.shape[-1] if pitch is None else pitch))
 
+    # truecolour plates: globe g = ring slots 4g .. 4g+3, slot 4g+c holds byte c of every texel
+    def upload_plate_rgba(self, globe, plate, src, pitch=None):
+        """src [ps, ps, 4] uint8 (or rows `pitch` bytes apart: any uint8 array whose rows are at least 4 * ps bytes)"""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if pitch is None:
+            pitch = src.shape[-1] * (src.shape[-2] if src.ndim == 3 else 1)
+        self._chk(lib.bk_upload_plate_rgba(self._h, globe, plate, _ptr(src), pitch))
+
+    def upload_plate_rgba_device(self, globe, plate, ptr, pitch):
+        self._chk(lib.bk_upload_plate_rgba_device(self._h, globe, plate, ptr, pitch))
+
     def globe_device_ptr(self, frame=0):
         return lib.bk_globe_device_ptr(self._h, frame)
 
@@ -415,6 +429,10 @@ class Context:
                 self._pal_ptr = (pal, arr, pp)
         self._chk(lib.bk_apply_device(self._h, frame0, nframes, dst_ptr, pitch, frame_stride, x0, y0,
                                       int(rubix_on), pp))
+
+    def apply_rgba_device(self, dst_ptr, pitch, frame_stride, globe0=0, nframes=1, x0=0, y0=0):
+        """truecolour frames (4 bytes per pixel) from truecolour globes; pitch / frame_stride in bytes, x0 / y0 in pixels"""
+        self._chk(lib.bk_apply_rgba_device(self._h, globe0, nframes, dst_ptr, pitch, frame_stride, x0, y0))
 
     # ---- the resident single-frame apply (bk_apply_resident_*): one kernel stays on the device, frames are commands
     def resident_begin(self, rubix_on=False, pal=None, idle_ms=0.0):

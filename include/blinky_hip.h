@@ -19,6 +19,10 @@
  *   - all device work is enqueued on the context's HIP stream (bk_set_stream);
  *     host-pointer entry points are synchronous with respect to their buffers.
  *   - there is no CPU fallback: without a usable GPU bk_create fails.
+ *   - texels and pixels are 8-bit palettised, as the reference's (TyrQuake's software rasteriser).  TRUECOLOUR - 32-bit plates
+ *     warped into 32-bit frames, for hosts whose plates are frame buffers of a present-day renderer - is bk_upload_plate_rgba /
+ *     bk_upload_plate_rgba_device / bk_apply_rgba_device: a 32-bit globe is four byte planes in four consecutive slots of the same
+ *     globe ring, so lens build, lensmap and everything else in this header are shared with the 8-bit path as they are.
  */
 #ifndef BLINKY_HIP_H
 #define BLINKY_HIP_H
@@ -202,6 +206,19 @@ int      bk_globe_rows(const bk_ctx *ctx);
 uint32_t bk_globe_texel_offset(const bk_ctx *ctx, int plate, int px, int py);
 /* synthetic plates: the SURVEY.md 8(d) LCG stream generated on the device */
 int   bk_fill_plate_lcg(bk_ctx *ctx, int frame, int plate, uint32_t seed_frame);
+/* TRUECOLOUR plates (no counterpart in the reference, whose plates are 8-bit; its README names GPU projection of plates captured in
+ * frame buffers as its future).  Truecolour globe g = ring slots 4g .. 4g+3 (bk_set_frames(4 * globes)); slot 4g+c holds byte c of
+ * every texel, in the tiled layout every slot has - so bk_fill_plate_lcg, bk_download_plate, bk_globe_device_ptr and
+ * bk_globe_texel_offset work per byte plane exactly as documented above.  The bytes are opaque: RGBA, BGRA or any other 4-byte
+ * texel.  src: ps rows of ps 32-bit texels, rows src_pitch_bytes (>= 4 * ps) apart.
+ * bk_upload_plate_rgba         src is host memory; synchronous with respect to src.  The plate travels through a device staging
+ *                              buffer of 4*ps*ps bytes, allocated on first use and freed with the context.
+ * bk_upload_plate_rgba_device  src is device memory (a renderer's frame buffer, best 16-byte aligned with a pitch that is a
+ *                              multiple of 16); the de-interleaving kernel is only enqueued on the context's stream: whatever wrote
+ *                              src must be ordered before it on that stream (or complete), and src stay untouched until it has run.
+ * Both end a resident session first, as every device entry point but the 8-bit plate uploads. */
+int   bk_upload_plate_rgba(bk_ctx *ctx, int globe, int plate, const uint8_t *src_host, int src_pitch_bytes);
+int   bk_upload_plate_rgba_device(bk_ctx *ctx, int globe, int plate, const void *src_dev, int src_pitch_bytes);
 
 /* ---- lensmap apply ------------------------------------------------------------------
  * replaces: render_lensmap (fisheye.c:2406-2424).  Unmapped pixels leave dst untouched.
@@ -223,6 +240,24 @@ int bk_apply_end(bk_ctx *ctx, uint8_t *dst, int dst_pitch, int x0, int y0);
 int bk_apply_device(bk_ctx *ctx, int frame0, int nframes, void *dst_dev, int dst_pitch,
                     size_t frame_stride, int x0, int y0, int rubix_on,
                     const uint8_t pal[BK_MAX_PLATES][256]);
+/* bk_apply_rgba_device: render_lensmap for TRUECOLOUR globes (bk_upload_plate_rgba*) - the same gather, four bytes per pixel.
+ * dst is device memory holding nframes frames of 32-bit pixels, frame_stride bytes apart; frame f is warped from truecolour globe
+ * (globe0 + f) % (resident slots / 4) and pixel (x, y) lands at dst + f*frame_stride + (y0+y)*dst_pitch + 4*(x0+x): x0 / y0 are in
+ * pixels, dst addresses pixel (0,0) of the WHOLE view, only the owned rows (bk_set_rows) are written and unmapped pixels are left
+ * untouched.  Asynchronous on the context's stream; a resident session is ended first, as by bk_apply_device.  One launch of the
+ * staged apply's block map (compiled and tuned as for 4 * nframes 8-bit frames): per frame the four byte planes are gathered through
+ * it and stored as whole pixels: the traffic of four 8-bit frames and, measured, their time (16 truecolour 3840x2160 frames against one
+ * 64-frame bk_apply_device launch over the same slots: 224.6 / 224.4 us cube/panini, 426.0 / 431.5 us cube/hammer; profiles/rgba_apply.txt).
+ * Alignment: dst, dst_pitch and frame_stride must be multiples of 4 bytes; make dst + 4 * x0, dst_pitch and frame_stride multiples
+ * of 16 - then fully mapped tiles leave as 16-byte stores that fill whole 128-byte lines; otherwise every pixel is a store of its own.
+ * BK_E_INVALID: dst_pitch < 4 * (W + x0), a negative origin, globe0 or nframes < 1, or dst / dst_pitch / frame_stride not a multiple
+ * of 4.  BK_E_STATE: no lensmap; fewer than 4 ring slots; bk_set_apply_variant(0) (the staged variant only, as for the resident
+ * apply); a BK_DEVICE_NONE context.
+ * Out of scope: rubix tints on truecolour frames; the resident kernel; a host-pointer bk_apply_rgba; the bk_comm_* / bk_multi_*
+ * exchanges, whose stripe buffers are W bytes per row (stripe CONTEXTS - bk_set_rows - do work); the drop-in fisheye_hip.c, whose
+ * engine is 8-bit; texel filtering (nearest texel, as everywhere). */
+int bk_apply_rgba_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch,
+                         size_t frame_stride, int x0, int y0);
 
 /* ---- resident single-frame apply ------------------------------------------------------------------------------------
  * replaces: the per-frame call of render_lensmap (fisheye.c:803 -> 2406-2424) for hosts whose globes stay in device memory.

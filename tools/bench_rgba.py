@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Truecolour apply against the 8-bit batch launch that moves the same bytes (GPU only).
+
+At 3840x2160 cube/panini and cube/hammer, over the 64-slot LCG ring of the bench's headline job:
+  A  one bk_apply_device launch of 64 8-bit frames into planar 8-bit frames (the 8-bit path, unchanged)
+  B  one bk_apply_rgba_device launch of 16 truecolour frames from the same slots (slot 4g+c = byte plane c of truecolour globe g)
+B's output is compared with A's plane by plane before anything is timed.  Timing: HIP events on the context's stream, warm-up
+launches first, regions of at least --region seconds made of ten event-timed trains of launches (a region's figure is the median
+train), A / B / A / B ... alternated --repeats times inside this one process.  The target: B's median <= A's median + A's own spread
+(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import torch  # noqa: E402
+
+import blinky_amd  # noqa: E402
+import scripts as S  # noqa: E402
+
+W, H, SLOTS = 3840, 2160, 64
+
+
+def region(stream, launch, per_train, trains=10):
+    """median over `trains` event-timed trains of `per_train` launches: seconds per launch"""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(trains + 1)]
+    ev[0].record(stream)
+    for t in range(trains):
+        for _ in range(per_train):
+            launch()
+        ev[t + 1].record(stream)
+    ev[-1].synchronize()
+    return statistics.median(ev[t].elapsed_time(ev[t + 1]) * 1e-3 / per_train for t in range(trains))
+
+
+def measure(lens, repeats, region_s):
+    ctx = blinky_amd.Context(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_frames(SLOTS)
+    S.configure(ctx, "cube", lens, None, (W, H))
+    ctx.build()
+    for f in range(SLOTS):
+        for p in range(6):
+            ctx.fill_plate_lcg(f, p, seed_frame=f)
+    out_a = torch.zeros((SLOTS, H, W), dtype=torch.uint8, device="cuda")
+    out_b = torch.zeros((SLOTS // 4, H, W, 4), dtype=torch.uint8, device="cuda")
+
+    def a():
+        ctx.apply_device(out_a.data_ptr(), W, H * W, frame0=0, nframes=SLOTS)
+
+    def b():
+        ctx.apply_rgba_device(out_b.data_ptr(), 4 * W, 4 * W * H, globe0=0, nframes=SLOTS // 4)
+
+    for _ in range(3):                                     # warm-up: the first launch compiles and tunes the block map both share
+        a()
+        b()
+    torch.cuda.synchronize()
+    # B against A, plane by plane: byte c of truecolour frame f = 8-bit frame 4f + c
+    planar = out_b.permute(0, 3, 1, 2).reshape(SLOTS, H, W)
+    if not torch.equal(planar, out_a):
+        bad = int((planar != out_a).sum())
+        raise SystemExit(f"{lens}: the truecolour frames differ from the 8-bit frames of the same slots in {bad} bytes - nothing timed")
+    del planar
+    # launches per train: a region of ten trains lasts at least region_s
+    pilot = min(region(stream, a, 4, trains=3), region(stream, b, 4, trains=3))
+    per_train = max(2, int(region_s / 10 / pilot) + 1)
+    ra, rb = [], []
+    for _ in range(repeats):
+        ra.append(region(stream, a, per_train))
+        rb.append(region(stream, b, per_train))
+    tm = ctx.traffic_model()
+    st = ctx.tile_stats()
+    ctx.close()
+    med_a, med_b, spread = statistics.median(ra), statistics.median(rb), max(ra) - min(ra)
+    visit = max(1, tm["frames_per_visit"] // 4)            # truecolour frames per block visit
+    # two byte models per truecolour frame, both with every mapped pixel stored once and the block map read once per visit: "staged" counts
+    # a globe line once per block that stages it, "compulsory" once per frame (DESIGN.md 3's model: L2 serves what blocks share)
+    bytes_frame = 4 * (tm["mapped_pixels"] + 128 * tm["staged_lines"]) + tm["blockmap_bytes_per_visit"] / visit
+    bytes_min = 4 * (tm["mapped_pixels"] + 128 * tm["unique_globe_lines"]) + tm["blockmap_bytes_per_visit"] / visit
+    return dict(lens=lens, W=W, H=H, block=f"128x{st['tile_h'] % 1000}", lds_kib=st["lds_bytes_per_wave"] // 1024, launches_per_train=per_train,
+                region_s=10 * per_train * med_a, a_regions_us=[t * 1e6 for t in ra], b_regions_us=[t * 1e6 for t in rb],
+                a_us=med_a * 1e6, b_us=med_b * 1e6, a_spread_us=spread * 1e6, b_over_a=med_b / med_a,
+                us_per_truecolour_frame=med_b * 1e6 / (SLOTS // 4), model_bytes_per_truecolour_frame=bytes_frame,
+                implied_tb_s=bytes_frame * (SLOTS // 4) / med_b / 1e12,
+                compulsory_bytes_per_truecolour_frame=bytes_min, compulsory_tb_s=bytes_min * (SLOTS // 4) / med_b / 1e12, target_met=bool(med_b <= med_a + spread))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lenses", default="panini,hammer")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--region", type=float, default=0.25, help="seconds per timed region (at least 0.2)")
+    ap.add_argument("--out", default=None, help="also write the results as JSON lines to this file")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_rgba.py measures on the GPU; there is none here")
+    rows = []
+    for lens in args.lenses.split(","):
+        r = measure(lens, args.repeats, max(0.2, args.region))
+        rows.append(r)
+        print(f"4K cube/{lens} [{r['block']} blocks, {r['lds_kib']} KiB staging], regions of {r['region_s']:.2f} s, {args.repeats} x A/B alternated:\n"
+              f"  A  64 8-bit frames      {r['a_us']:8.1f} us per launch (regions {', '.join('%.1f' % t for t in r['a_regions_us'])}; spread {r['a_spread_us']:.1f})\n"
+              f"  B  16 truecolour frames {r['b_us']:8.1f} us per launch (regions {', '.join('%.1f' % t for t in r['b_regions_us'])})\n"
+              f"  B / A = {r['b_over_a']:.3f}; {r['us_per_truecolour_frame']:.2f} us per truecolour frame; model {r['model_bytes_per_truecolour_frame'] / 1e6:.1f} MB per frame"
+              f" staged -> {r['implied_tb_s']:.2f} TB/s, {r['compulsory_bytes_per_truecolour_frame'] / 1e6:.1f} MB compulsory -> {r['compulsory_tb_s']:.2f} TB/s; "
+              f"target B <= A + spread: {'met' if r['target_met'] else 'MISSED'}", flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
