@@ -627,9 +627,11 @@ extern "C" __global__ __launch_bounds__(256) void bk_save_plate(BkBuildParams P,
 
 /* test / diagnosis hook: run one callback over an array of argument tuples and return the raw
  * double results (bk_debug_eval_device).  which: 0 lens_inverse, 1 lens_forward, 2 globe_plate.
- * nout[i] = number of results, -1 for a single nil, -100-err on a runtime error. */
+ * nout[i] = number of results, -1 for a single nil, -100-err on a runtime error.  bound / flag (either may be null,
+ * bk_debug_eval_device_bounds): the bound each returned number carries (0 for everything else) and whether the evaluation raised
+ * the flag - what tests/hostemu reads out of the same code on the host. */
 extern "C" __global__ __launch_bounds__(256) void bk_eval_callback(BkBuildParams P, int which, const double *args,
-                                                                   int nargs, int n, double *out, int *nout)
+                                                                   int nargs, int n, double *out, int *nout, double *bound, int *flag)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -650,5 +652,8 @@ extern "C" __global__ __launch_bounds__(256) void bk_eval_callback(BkBuildParams
 #endif
     for (int k = 0; k < BK_MAXRET; ++k) out[(size_t)i * BK_MAXRET + k] = (k < m && r[k].t == BK_TNUM) ? r[k].n : __builtin_nan("");
     nout[i] = S.err ? -100 - S.err : (m == 1 && r[0].t == BK_TNIL) ? -1 : m;
+    if (bound)
+        for (int k = 0; k < BK_MAXRET; ++k) bound[(size_t)i * BK_MAXRET + k] = (k < m && r[k].t == BK_TNUM) ? r[k].e : 0.0;
+    if (flag) flag[i] = S.flag;
 }
 #endif  /* !BK_HOST_MODULE */

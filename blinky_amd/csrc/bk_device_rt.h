@@ -28,6 +28,11 @@ typedef struct { double n; double e; int t; } bkv;
 #define BK_LIBM_REL 0x1p-50          /* assumed bound on |libm_ref(x) - bkm(x)| / |bkm(x)| (4 x 2^-52) */
 #endif
 #define BK_ROUND_REL 0x1p-51         /* one rounding on each side of an operation with inexact inputs */
+/* Relative bounds need room below the value: 2^-51 of a number under 2^-971 is a subnormal with few bits or none, and under 2^-1022 the
+ * operation's own rounding is absolute, not relative.  An INEXACT value of smaller magnitude than this (other than an exact 0) is not bounded: flagged.
+ * 2^-960 keeps every bound of an unflagged value a normal number with 52 bits to spare (bounds are >= 2^-52 of a value >= 2^-960).
+ * A libm RESULT is inexact whatever its argument: math.sin(1e-300) of an exact 1e-300 is flagged too (bk_elibm), on purpose. */
+#define BK_TINY 0x1p-960
 
 struct BkState {
     const BkBuildParams *P;
@@ -54,20 +59,35 @@ BK_DEV double bk_abs(double x) { return __builtin_fabs(x); }
 /* A NaN or infinity that arises from exact arguments arises on every libm alike (domain errors, overflow, x/0) and then
  * propagates by IEEE rules: it carries no bound.  One that arises from INEXACT arguments cannot be bounded: flagged. */
 BK_DEV bool bk_finite(double z) { return bk_abs(z) < BKM_INF; }
-/* bound after an IEEE operation whose inputs are inexact: propagated part + the two roundings (one fma; its result is finite
- * exactly when z and the propagated part are - overflow aside, which is flagged like them) */
+BK_DEV bool bk_tiny(double z) { return bk_abs(z) < BK_TINY && z != 0.0; }
+/* bound after an IEEE operation whose inputs ARE inexact (the caller has looked at their bounds: a propagated part that underflowed to 0
+ * is not "exact"): propagated part + the two roundings (one fma; its result is finite exactly when z and the propagated part are -
+ * overflow aside, which is flagged like them) */
+BK_DEV double bk_eop_inexact(BkState &S, double z, double eprop)
+{
+    const double r = __builtin_fma(bk_abs(z), BK_ROUND_REL, eprop);
+    if (!(r < BKM_INF) || bk_tiny(z)) { S.flag = 1; return 0.0; }
+    return r;
+}
+/* the same where the propagated part is a sum or a scaled copy of the inputs' bounds, 0 exactly when they all are: exact inputs, exact result */
 BK_DEV double bk_eop(BkState &S, double z, double eprop)
 {
     if (eprop == 0.0) return 0.0;
-    const double r = __builtin_fma(bk_abs(z), BK_ROUND_REL, eprop);
-    if (!(r < BKM_INF)) { S.flag = 1; return 0.0; }
-    return r;
+    return bk_eop_inexact(S, z, eprop);
+}
+/* a product of two bookkeeping terms that the bound cannot do without: one that leaves the normal range has lost the bits it was for */
+BK_DEV double bk_eprod(BkState &S, double a, double b)
+{
+    const double p = a * b;
+    if (!(p >= 0x1p-1022) && a != 0.0 && b != 0.0) S.flag = 1;
+    return p;
 }
 /* bound after a libm call: propagated part + the libm discrepancy itself (also for exact inputs) */
 BK_DEV double bk_elibm(BkState &S, double z, double eprop)
 {
     const double r = __builtin_fma(bk_abs(z), BK_LIBM_REL, eprop);
     if (!(r < BKM_INF)) { if (eprop != 0.0) S.flag = 1; return 0.0; }
+    if (bk_tiny(z)) { S.flag = 1; return 0.0; }
     return r;
 }
 /* A step of a self-correcting iteration (bk_emit.cpp, contraction_pattern): the variable carried from step to step entered this
@@ -117,13 +137,15 @@ BK_DEV bkv bk_mul(BkState &S, bkv a, bkv b)
 {
     const double x = bk_tonum(S, a), y = bk_tonum(S, b), z = x * y;
     if (a.e == 0.0 && b.e == 0.0) return bk_num(z);
-    return bk_nume(z, bk_eop(S, z, bk_abs(x) * b.e + bk_abs(y) * a.e + a.e * b.e));
+    if (z == 0.0 && x != 0.0 && y != 0.0) S.flag = 1;                /* underflow: whether another libm's product is 0 too is not known */
+    return bk_nume(z, bk_eop_inexact(S, z, bk_abs(x) * b.e + bk_abs(y) * a.e + a.e * b.e));
 }
 BK_DEV double bk_ediv(BkState &S, double x, double ex, double y, double ey, double z)
 {
     if (ex == 0.0 && ey == 0.0) return 0.0;
     if (!(bk_abs(y) > 2.0 * ey)) { S.flag = 1; return 0.0; }        /* the divisor's sign / magnitude is not determined */
-    return bk_eop(S, z, (ex + bk_abs(z) * ey) / (bk_abs(y) - ey));
+    if (z == 0.0 && x != 0.0 && bk_finite(y)) S.flag = 1;           /* underflow, as in bk_mul */
+    return bk_eop_inexact(S, z, (ex + bk_eprod(S, bk_abs(z), ey)) / (bk_abs(y) - ey));
 }
 BK_DEV bkv bk_div(BkState &S, bkv a, bkv b)
 {
@@ -136,7 +158,7 @@ BK_DEV bkv bk_mod(BkState &S, bkv a, bkv b)       /* luai_nummod: a - floor(a/b)
     const double q = x / y, fl = bkm_floor(q), z = x - fl * y;
     if (a.e == 0.0 && b.e == 0.0) return bk_num(z);
     bk_need_same_floor(S, q, bk_ediv(S, x, a.e, y, b.e, q));
-    return bk_nume(z, bk_eop(S, z, a.e + bk_abs(fl) * b.e) + bk_abs(fl * y) * BK_ROUND_REL);
+    return bk_nume(z, bk_eop_inexact(S, z, a.e + bk_abs(fl) * b.e) + bk_abs(fl * y) * BK_ROUND_REL);
 }
 /* z = x ^ y through bkm_pow (glibc's pow on the reference side) */
 BK_DEV bkv bk_powv(BkState &S, bkv a, bkv b)
@@ -148,9 +170,10 @@ BK_DEV bkv bk_powv(BkState &S, bkv a, bkv b)
         double m = 1.0;
         for (int k = 1; k < (int)y; ++k) m *= bk_abs(x) + a.e;
         ep = 2.0 * y * m * a.e;
+        if (z == 0.0 && x != 0.0) S.flag = 1;                                                      /* underflow */
     } else if (a.e != 0.0 || b.e != 0.0) {
         /* d(x^y) = x^y (y dx/x + ln x dy); only for a base safely away from 0 and a finite result */
-        if (!(x - 2.0 * a.e > 0.0) || !(bk_abs(z) < BKM_INF)) { S.flag = 1; return bk_num(z); }
+        if (!(x - 2.0 * a.e > 0.0) || !(bk_abs(z) < BKM_INF) || z == 0.0) { S.flag = 1; return bk_num(z); }     /* (0: underflow) */
         ep = 2.0 * bk_abs(z) * (bk_abs(y) * a.e / (x - a.e) + (bk_abs(bkm_log(x)) + 1.0) * b.e);
     }
     return bk_nume(z, bk_elibm(S, z, ep));
@@ -262,7 +285,7 @@ BK_DEV bkv bk_f_sqrt(BkState &S, bkv a)                                    /* IE
     const double x = bk_tonum(S, a), z = bkm_sqrt(x);
     if (a.e == 0.0) return bk_num(z);
     if (!(x - 2.0 * a.e > 0.0)) { S.flag = 1; return bk_num(z); }
-    return bk_nume(z, bk_eop(S, z, a.e / (2.0 * bkm_sqrt(x - a.e))));
+    return bk_nume(z, bk_eop_inexact(S, z, a.e / (2.0 * bkm_sqrt(x - a.e))));
 }
 BK_DEV bkv bk_f_abs(BkState &S, bkv a) { return bk_nume(bkm_fabs(bk_tonum(S, a)), a.e); }
 BK_DEV bkv bk_f_floor(BkState &S, bkv a) { const double x = bk_tonum(S, a); bk_need_same_floor(S, x, a.e); return bk_num(bkm_floor(x)); }
@@ -270,9 +293,9 @@ BK_DEV bkv bk_f_ceil(BkState &S, bkv a) { const double x = bk_tonum(S, a); bk_ne
 BK_DEV double bk_e_atan2(BkState &S, double y, double ey, double x, double ex)
 {
     if (ex == 0.0 && ey == 0.0) return 0.0;
-    const double d = x * x + y * y, w = bk_abs(x) * ey + bk_abs(y) * ex, s = ex + ey;
-    /* the point must stay clear of the origin and of the branch cut along the negative x axis */
-    if (!(d > 16.0 * s * s) || (x < 0.0 && !(bk_abs(y) > ey))) { S.flag = 1; return 0.0; }
+    const double d = x * x + y * y, w = bk_eprod(S, bk_abs(x), ey) + bk_eprod(S, bk_abs(y), ex), s = ex + ey;
+    /* the point must stay clear of the origin and of the branch cut along the negative x axis (and d within the normal range: 2w / d) */
+    if (!(d > 16.0 * s * s) || (x < 0.0 && !(bk_abs(y) > ey)) || !(d >= 0x1p-1022 && d < BKM_INF)) { S.flag = 1; return 0.0; }
     return 2.0 * w / d;
 }
 BK_DEV bkv bk_f_atan2(BkState &S, bkv a, bkv b)
@@ -288,7 +311,7 @@ BK_DEV bkv bk_f_fmod(BkState &S, bkv a, bkv b)                             /* C 
     if (a.e == 0.0 && b.e == 0.0) return bk_num(z);
     const double q = x / y;
     bk_need_same_trunc(S, q, bk_ediv(S, x, a.e, y, b.e, q));
-    return bk_nume(z, bk_eop(S, z, a.e + bk_abs(bkm_trunc(q)) * b.e));
+    return bk_nume(z, bk_eop_inexact(S, z, a.e + bk_abs(bkm_trunc(q)) * b.e));
 }
 BK_DEV bkv bk_f_scale(BkState &S, bkv a, double c, bool divide)            /* math.deg / math.rad */
 {
@@ -313,7 +336,7 @@ BK_DEV void bk_f_modf(BkState &S, bkv a, bkv *r)
     const double x = bk_tonum(S, a), ip = bkm_trunc(x);
     bk_need_same_trunc(S, x, a.e);
     r[0] = bk_num(ip);
-    r[1] = bk_nume(bkm_isinf(x) ? bkm_copysign(0.0, x) : x - ip, a.e);
+    r[1] = bk_nume(bkm_copysign(bkm_isinf(x) ? 0.0 : x - ip, x), a.e);     /* C modf: a zero fraction has the argument's sign */
 }
 
 /* ---- mathlib.c / fisheye.c helpers, float arithmetic exactly as the reference (no FMA) ---- */
@@ -390,7 +413,7 @@ BK_DEV int bk_host_ray_to_latlon(BkState &S, bkv x, bkv y, bkv z, bkv *r)      /
 BK_DEV int bk_host_plate_to_ray(BkState &S, bkv plate, bkv u, bkv v, bkv *r)
 {
     bk_need_same_trunc(S, bk_tonum(S, plate), plate.e);
-    int pi = (int)bk_tonum(S, plate);            /* int plate_index = luaL_checknumber(...)  :1523 */
+    int pi = bk_trunc_to_int(bk_tonum(S, plate)); /* int plate_index = luaL_checknumber(...)  :1523 (a NaN plate is INT_MIN there, 0 to the GPU's own conversion) */
     float ray[3];
     if (pi < 0 || pi >= S.P->numplates) { r[0] = bk_nil(); return 1; }
     /* u, v are narrowed by VectorMA's float scale after the double subtraction of 0.5 (:1209-1211) */

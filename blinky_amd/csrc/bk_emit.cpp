@@ -1245,7 +1245,8 @@ struct Emitter {
             line(f, "{");
             f.indent++;
             Args a = emit_args(f, s.exprs);
-            if (a.fixed.size() > 8 || (a.multi && a.fixed.size() > 4)) unsupported(f.chunk, s.line, "more than 8 return values");
+            if (a.fixed.size() > 8) unsupported(f.chunk, s.line, "more than 8 return values");
+            if (a.multi && a.fixed.size() > 4) unsupported(f.chunk, s.line, "more than 4 return values in front of a trailing call or `...`");
             for (size_t i = 0; i < a.fixed.size(); ++i) line(f, "r[" + std::to_string(i) + "] = " + a.fixed[i] + ";");
             if (a.multi) {
                 line(f, "for (int q = 0; q < " + a.mcnt + " && " + std::to_string(a.fixed.size()) + " + q < BK_MAXRET; ++q) r[" + std::to_string(a.fixed.size()) + " + q] = " + a.marr + "[q];");

@@ -1079,6 +1079,7 @@ extern "C" int bk_debug_eval(bk_ctx *ctx, int which, const double *args, int nar
     try {
         Values a;
         for (int i = 0; i < nargs; ++i) a.push_back(Value::number(args[i]));
+        P->interp.steps = 0;                                         // (the budget is per call, as in HostEval::call: one runaway evaluation must not fail the next)
         Values r = P->interp.call(f, a);
         *nout = (int)r.size();
         for (size_t i = 0; i < r.size() && i < 8; ++i) out[i] = r[i].t == Value::NUM ? r[i].n : __builtin_nan("");
@@ -2484,7 +2485,7 @@ extern "C" int bk_save_plate(bk_ctx *ctx, int frame, int plate, int with_margins
 }
 
 #if BK_DEBUG_API
-extern "C" int bk_debug_eval_device(bk_ctx *ctx, int which, const double *args, int nargs, int n, double *out, int *nout)
+static int eval_device(bk_ctx *ctx, int which, const double *args, int nargs, int n, double *out, int *nout, double *bound, int *flag)
 {
     if (!ctx || !args || !out || !nout || nargs < 1 || nargs > 4 || n < 1) return BK_E_INVALID;
     if (ctx->device < 0) return ctx->fail(BK_E_STATE, "this context has no device");
@@ -2499,19 +2500,36 @@ extern "C" int bk_debug_eval_device(bk_ctx *ctx, int which, const double *args, 
     BK_HIP(ctx, hipModuleGetFunction(&fn, P->module, "bk_eval_callback"));
     BkBuildParams bp;
     fill_params(ctx, &bp);
-    double *d_args = nullptr, *d_out = nullptr;
-    int *d_nout = nullptr;
-    BK_HIP(ctx, hipMalloc((void **)&d_args, sizeof(double) * nargs * n));
-    BK_HIP(ctx, hipMalloc((void **)&d_out, sizeof(double) * 8 * n));
-    BK_HIP(ctx, hipMalloc((void **)&d_nout, sizeof(int) * n));
+    // one allocation: args [n * nargs], out [8 n], bound [8 n] (doubles), then nout [n], flag [n] (ints)
+    // (the ints come last, so every region is aligned for its type; bound and flag are laid out whether or not the caller reads them)
+    const size_t nd = (size_t)n * (size_t)(nargs + 16);
+    double *d_args = nullptr;
+    BK_HIP(ctx, hipMalloc((void **)&d_args, sizeof(double) * nd + sizeof(int) * 2 * (size_t)n));
+    const DeviceMem mem(d_args);
+    double *d_out = d_args + (size_t)n * nargs, *d_bound = d_out + (size_t)n * 8;
+    int *d_nout = (int *)(d_bound + (size_t)n * 8), *d_flag = d_nout + n;
+    double *k_bound = bound ? d_bound : nullptr;
+    int *k_flag = flag ? d_flag : nullptr;
     BK_HIP(ctx, hipMemcpyAsync(d_args, args, sizeof(double) * nargs * n, hipMemcpyHostToDevice, ctx->stream));
-    void *kargs[] = {&bp, &which, &d_args, &nargs, &n, &d_out, &d_nout};
+    void *kargs[] = {&bp, &which, &d_args, &nargs, &n, &d_out, &d_nout, &k_bound, &k_flag};
     hipError_t e = hipModuleLaunchKernel(fn, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, ctx->stream, kargs, nullptr);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(nout, d_nout, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_args); (void)hipFree(d_out); (void)hipFree(d_nout);
+    if (e == hipSuccess && bound) e = hipMemcpyAsync(bound, d_bound, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && flag) e = hipMemcpyAsync(flag, d_flag, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);         // (always, before the buffer goes)
+    if (e == hipSuccess) e = es;
     if (e != hipSuccess) return ctx->fail(BK_E_HIP, "bk_debug_eval_device: %s", hipGetErrorString(e));
     return BK_OK;
+}
+extern "C" int bk_debug_eval_device(bk_ctx *ctx, int which, const double *args, int nargs, int n, double *out, int *nout)
+{
+    return eval_device(ctx, which, args, nargs, n, out, nout, nullptr, nullptr);
+}
+extern "C" int bk_debug_eval_device_bounds(bk_ctx *ctx, int which, const double *args, int nargs, int n, double *out, double *bound, int *flag,
+                                           int *nout)
+{
+    if (!bound || !flag) return BK_E_INVALID;
+    return eval_device(ctx, which, args, nargs, n, out, nout, bound, flag);
 }
 #endif

@@ -1812,7 +1812,7 @@ Interp::Interp(const MathLib &m) : math(&m)
     register_builtin("math.modf", [](Interp &, const Values &a, Values &r) {
         double x = argnum(a, 0, "modf"), ip = std::trunc(x);
         r.push_back(Value::number(ip));
-        r.push_back(Value::number(std::isinf(x) ? std::copysign(0.0, x) : x - ip));
+        r.push_back(Value::number(std::copysign(std::isinf(x) ? 0.0 : x - ip, x)));     // C modf: a zero fraction has the argument's sign
     });
     register_builtin("math.max", [](Interp &, const Values &a, Values &r) {
         double m = argnum(a, 0, "max");

@@ -127,6 +127,7 @@ _SIGS = {
     "bk_script_console": (C.c_char_p, [_vp]),
     "bk_set_host_math": (_i, [_vp, _i]),
     "bk_debug_eval_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
+    "bk_debug_eval_device_bounds": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "bk_dev_alloc": (_vp, [_vp, _sz]),
     "bk_dev_free": (None, [_vp, _vp]),
     "bk_dev_read": (_i, [_vp, _vp, _vp, _sz]),
@@ -587,6 +588,15 @@ class Context:
         nout = np.empty(n, np.int32)
         self._chk(lib.bk_debug_eval_device(self._h, which, _ptr(args), nargs, n, _ptr(out), _ptr(nout)))
         return out, nout
+
+    def eval_device_bounds(self, which, args):
+        """eval_device with the device's bookkeeping: (out [n, 8], bound [n, 8] float64, flag [n], nout [n] int32)"""
+        args = np.ascontiguousarray(args, dtype=np.float64)
+        n, nargs = args.shape
+        out, bound = np.empty((n, 8), np.float64), np.empty((n, 8), np.float64)
+        flag, nout = np.empty(n, np.int32), np.empty(n, np.int32)
+        self._chk(lib.bk_debug_eval_device_bounds(self._h, which, _ptr(args), nargs, n, _ptr(out), _ptr(bound), _ptr(flag), _ptr(nout)))
+        return out, bound, flag, nout
 
     def eval_host_many(self, which, args):
         args = np.ascontiguousarray(args, dtype=np.float64)

@@ -91,6 +91,11 @@ int         bk_debug_eval(bk_ctx *ctx, int which, const double *args, int nargs,
 /* the same on the DEVICE (the generated code), over n argument tuples of nargs doubles: out gets 8
  * doubles per tuple, nout the result count (-1 = a single nil, <= -100 = runtime error bits) */
 int         bk_debug_eval_device(bk_ctx *ctx, int which, const double *args, int nargs, int n, double *out, int *nout);
+/* the same with the device's exactness bookkeeping (bk_device_rt.h) made visible: bound gets 8 doubles per tuple - the bound e each
+ * returned number carries, 0 for everything else - and flag one int per tuple, whether the evaluation raised the flag (a discrete
+ * decision inside the script depended on libm's last bits).  What tests/hostemu computes on the host must be what the device computes. */
+int         bk_debug_eval_device_bounds(bk_ctx *ctx, int which, const double *args, int nargs, int n, double *out, double *bound, int *flag,
+                                        int *nout);
 /* where the last bk_build's time went: out = {bk_last_build_ms (HIP events around the whole build: kernels + host fix-up),
  * wall ms of the host re-evaluation of the flagged entries inside it, flagged entries, worker threads of the fix-up pool,
  * wall ms of the inverse kernel launch(es) + read-back and sorting of the flag list, kernel re-runs because the list grew

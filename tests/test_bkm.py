@@ -9,13 +9,13 @@ import mpmath as mp
 import numpy as np
 import pytest
 
+from libm_probes import N, TRIG, logu, rng, seam_atan, seam_atan2, seam_fmod, seam_trig, u
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = C.CDLL(os.path.join(ROOT, "blinky_amd", "libbkm_host.so"))
 lib.bkmh_map1.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_long]
 lib.bkmh_map2.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
 mp.mp.prec = 220
-rng = np.random.default_rng(20240924)
-N = 700
 
 
 def f1(name, xs):
@@ -41,16 +41,6 @@ def err_ulps(got, exact):
     return float(abs(mp.mpf(got) - exact) / mp.mpf(u))
 
 
-def u(a, b, n=N):
-    return rng.uniform(a, b, n)
-
-
-def logu(a, b, n=N):
-    return np.exp(rng.uniform(math.log(a), math.log(b), n)) * rng.choice([-1.0, 1.0], n)
-
-
-TRIG = lambda: np.concatenate([u(-10, 10), logu(1e-8, 1e6), logu(1e6, 1e300, N // 4),
-                               np.arange(1, 120) * math.pi / 2, np.arange(1, 120) * math.pi / 32])
 CASES1 = {
     "sin": (TRIG, mp.sin), "cos": (TRIG, mp.cos), "tan": (TRIG, mp.tan),
     "atan": (lambda: np.concatenate([u(-3, 3), logu(1e-9, 1e9)]), mp.atan),
@@ -146,26 +136,19 @@ def test_round4_rewrites_at_their_seams():
     def worst1(name, xs, exact):
         return max(err_ulps(float(g), exact(mp.mpf(float(x)))) for x, g in zip(xs, f1(name, xs)))
     # multiples of pi/32 and their neighbours, both sides of 2^16
-    k = np.arange(-3000, 3000)
-    near = np.concatenate([k * math.pi / 32 + d for d in (0.0, 1e-9, -1e-13, 3e-16)])
-    edge = np.concatenate([65536.0 + rng.uniform(-40, 40, 400), -65536.0 + rng.uniform(-40, 40, 400), [65535.99999999999, 65536.0, 65536.00000000001]])
+    near, edge = seam_trig()
     for nm, ex in (("sin", mp.sin), ("cos", mp.cos), ("tan", mp.tan)):
         assert worst1(nm, np.concatenate([near, edge]), ex) < 0.52, nm
     # atan: the table's decision points i/8 - 1/16 (+ the 2^-13 bias), both sides, and their reciprocals
-    pts = (np.arange(1, 17) - 0.5) / 8.0
-    at = np.concatenate([pts + d for d in (0.0, 2.0 ** -13, -2.0 ** -13, 1e-15, -1e-15)])
-    at = np.concatenate([at, 1.0 / at[at > 0], [1.0, 1.0 - 2.0 ** -53, 1.0 + 2.0 ** -52]])
+    at = seam_atan()
     assert worst1("atan", at, mp.atan) < 0.52
     assert worst1("asin", np.concatenate([at[at <= 1], [math.sqrt(0.5), 0.7071067811865475, 0.7071067811865477]]), mp.asin) < 0.52
     assert worst1("acos", np.concatenate([at[at <= 1], -at[at <= 1], [math.sqrt(0.5), -math.sqrt(0.5)]]), mp.acos) < 0.52
     # atan2 at the ends of the exponent range and across the "quotient below 2^-59" switch
-    ys = np.array([5e-324, 1e-310, 1e-300, 1e300, 1.7e308, 1e-320, 3.0, 1e-17, 1e-18, 2.0 ** -60, 2.0 ** -61, 1e308, 1e-308, 1e-308, 4e-324])
-    xs = np.array([5e-324, 3e-310, 1e300, 1e-300, 1.7e308, 1e-322, -1e-320, 1.0, 1.0, 1.0, 1.0, -1e308, 1e308, -1e-308, 1e-323])
+    ys, xs = seam_atan2()
     for sy in (1.0, -1.0):
         got = f2("atan2", sy * ys, xs)
         assert max(err_ulps(float(g), mp.atan2(mp.mpf(float(sy * y)), mp.mpf(float(x)))) for x, y, g in zip(xs, ys, got)) < 0.52
     # fmod: the fma path, its fallback above 2^52, subnormals
-    n = 100000
-    fx = np.concatenate([rng.uniform(-1e4, 1e4, n), logu(1e-300, 1e300, n // 2), rng.integers(0, 2 ** 53, n // 2).astype(float), logu(1e-320, 1e-305, 2000), [2.0 ** 60, 2.0 ** 53 + 2, 7.0]])
-    fy = np.concatenate([rng.uniform(-9, 9, n), logu(1e-300, 1e300, n // 2), rng.integers(1, 2 ** 20, n // 2).astype(float), logu(1e-320, 1e-305, 2000), [3.0, 3.0, 2.0 ** -1074]])
+    fx, fy = seam_fmod(100000)
     assert (f2("fmod", fx, fy).view(np.uint64) == np.fmod(fx, fy).view(np.uint64)).all()
