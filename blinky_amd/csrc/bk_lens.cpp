@@ -181,6 +181,16 @@ static LensProgram *prog_of(bk_ctx *ctx)
     return ctx->prog;
 }
 
+// LensProgram::emitted is keyed on the interpreter's activity count, which Interp::run / set_global move.  The translation unit is
+// generated from the three callback roots as well (BK_HAS_GLOBE_PLATE and LF_globe_plate, which of the lens kernels exist), and a call
+// that replaces a root WITHOUT running script code - bk_set_globe_plates, bk_clear_globe, bk_clear_lens - leaves the count where it is,
+// bk_build's KeepActivity having rewound it to the very value the answer was remembered at: the answer is forgotten here instead, and
+// the next generate_source / build_module_ready emits again (and re-arms KeepActivity at the count of that moment).
+static void roots_changed(LensProgram *P)
+{
+    if (P) P->emitted.valid = false;
+}
+
 static void fill_plate(const MathLib &M, bk_plate &p, const double fwd[3], const double up[3], double fov_deg, bool *fov_ok)
 {
     for (int j = 0; j < 3; ++j) p.forward[j] = (float)fwd[j];                  /* fisheye.c:1818 */
@@ -269,7 +279,7 @@ extern "C" int bk_set_globe_plates(bk_ctx *ctx, const bk_plate *plates, int nump
     for (int i = 0; i < numplates; ++i) ctx->plates[i] = plates[i];
     ctx->numplates = numplates;
     ctx->globe_valid = true;
-    if (ctx->prog) ctx->prog->globe_plate = Value();
+    if (ctx->prog) { ctx->prog->globe_plate = Value(); bk::roots_changed(ctx->prog); }
     return BK_OK;
 }
 
@@ -325,7 +335,7 @@ extern "C" int bk_load_lens(bk_ctx *ctx, const char *src, size_t len, const char
 extern "C" int bk_clear_lens(bk_ctx *ctx)
 {
     if (!ctx) return BK_E_INVALID;
-    if (ctx->prog) { ctx->prog->lens_valid = false; ctx->prog->lens_inverse = ctx->prog->lens_forward = Value(); }
+    if (ctx->prog) { ctx->prog->lens_valid = false; ctx->prog->lens_inverse = ctx->prog->lens_forward = Value(); bk::roots_changed(ctx->prog); }
     return BK_OK;
 }
 
@@ -334,7 +344,7 @@ extern "C" int bk_clear_globe(bk_ctx *ctx)
     if (!ctx) return BK_E_INVALID;
     ctx->globe_valid = false;
     ctx->numplates = 0;
-    if (ctx->prog) ctx->prog->globe_plate = Value();
+    if (ctx->prog) { ctx->prog->globe_plate = Value(); bk::roots_changed(ctx->prog); }
     return BK_OK;
 }
 

@@ -233,6 +233,14 @@ class Context:
         b = src.encode() if isinstance(src, str) else src
         self._chk(lib.bk_load_lens(self._h, b, len(b), name.encode()))
 
+    def clear_lens(self):
+        """lens.valid = false: the next build() raises "not a valid lens" over an empty lensmap"""
+        self._chk(lib.bk_clear_lens(self._h))
+
+    def clear_globe(self):
+        """globe.valid = false, no plates: the next build() raises "not a valid globe" over an empty lensmap"""
+        self._chk(lib.bk_clear_globe(self._h))
+
     def lens_info(self):
         info = LensInfo()
         self._chk(lib.bk_get_lens_info(self._h, C.byref(info)))

@@ -104,7 +104,12 @@ int bk_clear_lens(bk_ctx *ctx);    /* lens.valid = false ("not a valid lens", fi
 int bk_clear_globe(bk_ctx *ctx);   /* globe.valid = false (fisheye.c:1157-1160) */
 int bk_get_lens_info(const bk_ctx *ctx, bk_lens_info *out);
 int bk_get_globe(const bk_ctx *ctx, bk_plate plates[BK_MAX_PLATES], int *numplates);
-/* bypass the script for the globe (plates already in LUA_load_globe's float form) */
+/* bypass the script for the globe (plates already in LUA_load_globe's float form).  The call replaces the plates and drops a globe
+ * script's globe_plate function (plates are then chosen by the dot product, fisheye.c:1572-1590); the next bk_build generates its
+ * kernels for that.  It runs no script code and leaves the script state alone: the script global `numplates` is set by bk_load_lens,
+ * so a lens whose CHUNK reads it (lenses/debug.lua lays its grid out from it) keeps the layout of the plate count it was loaded
+ * under until the caller loads it again, as the reference does after every f_globe (fisheye.c:730-741).  plate_to_ray and every per-pixel
+ * callback see the new plates at once. */
 int bk_set_globe_plates(bk_ctx *ctx, const bk_plate *plates, int numplates);
 
 /* ---- geometry / parameters ------------------------------------------------------
