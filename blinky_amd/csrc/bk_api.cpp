@@ -241,6 +241,7 @@ extern "C" int bk_resize(bk_ctx *ctx, int width, int height)
 {
     if (!ctx) return BK_E_INVALID;
     if (width <= 0 || height <= 0) return ctx->fail(BK_E_INVALID, "bk_resize: bad size %dx%d", width, height);
+    ctx->clear_debug_corners();                 // (a test's corner table was sized for the platesize that was)
     if (ctx->device < 0) {                      // host-only: geometry for calc_zoom / code generation
         if (width == ctx->W && height == ctx->H) return BK_OK;      // (as with a device: the size it has already changes nothing, a stripe stays)
         ctx->W = width; ctx->H = height; ctx->ps = std::min(width, height); ctx->gp = (ctx->ps + 63) & ~63;

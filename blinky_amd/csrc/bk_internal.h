@@ -107,6 +107,18 @@ struct bk_ctx {
     bool fwd_tiles_used = false;         // the last build's quad pass went by bk_forward_tiles' flags (bk_debug_forward_tiles)
     void *fwd_tables = nullptr;          // BkBuildParams::fwd_quot + fwd_uv for platesize fwd_tables_ps (bk_lens.cpp)
     int fwd_tables_ps = -1;
+    // bk_debug_set_forward_corners (tests): a host copy of a texel-corner table that the forward build on the device uploads in place
+    // of its corner pass
+#if BK_DEBUG_API
+    std::vector<int32_t> dbg_corner_xy;
+    std::vector<uint8_t> dbg_corner_ok;
+    bool dbg_corners_set = false;
+    void clear_debug_corners() { dbg_corner_xy.clear(); dbg_corner_ok.clear(); dbg_corners_set = false; }
+    bool debug_corners_set() const { return dbg_corners_set; }
+#else
+    void clear_debug_corners() {}
+    bool debug_corners_set() const { return false; }
+#endif
     int last_flagged = 0, last_changed = 0;   // of the last bk_build: entries re-evaluated on the host / entries that changed
     uint8_t *h_frame = nullptr;      // pinned, [row1-row0][W]
     uint64_t *h_mask = nullptr;      // pinned

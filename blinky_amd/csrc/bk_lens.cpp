@@ -219,6 +219,7 @@ extern "C" int bk_load_globe(bk_ctx *ctx, const char *src, size_t len, const cha
     I.set_global("globe_plate", Value());
     ctx->numplates = 0;
     ctx->globe_valid = false;
+    ctx->clear_debug_corners();                       // (a test's corner table was sized for the plates that are going)
     P->globe_plate = Value();
     try {
         I.run(std::string(src, len), name);
@@ -279,6 +280,7 @@ extern "C" int bk_set_globe_plates(bk_ctx *ctx, const bk_plate *plates, int nump
     for (int i = 0; i < numplates; ++i) ctx->plates[i] = plates[i];
     ctx->numplates = numplates;
     ctx->globe_valid = true;
+    ctx->clear_debug_corners();
     if (ctx->prog) { ctx->prog->globe_plate = Value(); bk::roots_changed(ctx->prog); }
     return BK_OK;
 }
@@ -2005,6 +2007,13 @@ static int build_forward_device(bk_ctx *ctx, LensProgram *P, const std::string &
     const size_t px = (size_t)ctx->W * ctx->rows();
     const size_t n1 = (size_t)ctx->ps + 1;
     const size_t ncorner = (size_t)ctx->numplates * n1 * n1;
+    // bk_debug_set_forward_corners: the test's table goes where the corner pass would have put its own
+    const bool given = ctx->debug_corners_set();
+    (void)given;
+#if BK_DEBUG_API
+    if (given && ctx->dbg_corner_ok.size() != ncorner)
+        return ctx->fail(BK_E_INVALID, "bk_debug_set_forward_corners: the table has %zu corners, this build has %zu (plates * (platesize + 1)^2)", ctx->dbg_corner_ok.size(), ncorner);
+#endif
     const size_t want[4] = {ncorner * 2 * sizeof(int), ncorner, px * 4, px * 4};
     for (int k = 0; k < 4; ++k)
         if (ctx->fwd_scratch_bytes[k] < want[k]) {
@@ -2045,7 +2054,13 @@ static int build_forward_device(bk_ctx *ctx, LensProgram *P, const std::string &
         hipError_t e = hipMemsetAsync(ctx->fwd_scratch[2], 0, px * 4, st);
         return e == hipSuccess ? hipMemsetAsync(ctx->fwd_scratch[3], 0, px * 4, st) : e;
     };
-    const auto launch_corners = [&] {
+    const auto launch_corners = [&]() -> hipError_t {
+#if BK_DEBUG_API
+        if (given) {
+            hipError_t e = hipMemcpyAsync(bp.corner_xy, ctx->dbg_corner_xy.data(), ncorner * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+            return e == hipSuccess ? hipMemcpyAsync(bp.corner_ok, ctx->dbg_corner_ok.data(), ncorner, hipMemcpyHostToDevice, ctx->stream) : e;
+        }
+#endif
         return hipModuleLaunchKernel(P->k_corners, (unsigned)((n1 + 255) / 256), (unsigned)n1, (unsigned)ctx->numplates, 256, 1, 1, 0, ctx->stream, args, nullptr);
     };
     const auto launch_quads = [&](bool keys_cleared = false, void **with = nullptr) -> hipError_t {
@@ -2208,9 +2223,15 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
     if (int r = bk_calc_zoom(ctx, scale_out)) return r;                                        /* :2376 */
     if (P->info.map_type == BK_MAP_NONE) return ctx->fail(BK_E_STATE, "no inverse or forward map being used");   /* :2395 */
 
+    // a table from bk_debug_set_forward_corners and a build that would never read it (a host path, an inverse map): the test that set
+    // it would be looking at the lens's own map - an error instead, before any work, over the empty map `empty_unless_built` leaves
+    const auto unread_table = [&] {
+        return ctx->fail(BK_E_STATE, "bk_build: a corner table is set (bk_debug_set_forward_corners) and this build does not run the forward passes on the device");
+    };
     std::string src, refused;
     if (keep_activity.armed) P->interp.activity = keep_activity.at;      // (calc_zoom ran the callbacks: they are stateless)
     if (int r = generate_source(ctx, P, &src, &refused)) return r;
+    if (!refused.empty() && ctx->debug_corners_set()) return unread_table();
     if (!refused.empty()) { empty_unless_built.now(); return build_on_host(ctx, P, refused, display_out); }     // callbacks the emitter declines: the interpreter evaluates them
     if (int r = compile_module(ctx, P, src)) return r;
     if (int r = alloc_flag_buffers(ctx)) return r;
@@ -2224,6 +2245,7 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
         rq.interp = &P->interp; rq.lens_inverse = P->lens_inverse; rq.lens_forward = P->lens_forward; rq.globe_plate = P->globe_plate;
         std::string which;
         if (ctx->sequential_build >= 2 || bk::callbacks_carry_state(rq, &which)) {
+            if (ctx->debug_corners_set()) return unread_table();
             ctx->last_build_path = 2;
             ctx->last_build_why = ctx->sequential_build >= 2 ? "bk_set_sequential_build 2" : "state carried in '" + which + "'";
             empty_unless_built.now();
@@ -2233,6 +2255,7 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
             return build_forward_host(ctx, P, bp, true, display_out);
         }
     }
+    if (P->info.map_type != BK_MAP_FORWARD && ctx->debug_corners_set()) return unread_table();
     for (hipEvent_t &e : ctx->build_time_ev) if (!e) BK_HIP(ctx, hipEventCreate(&e));
     int counters[kNumCounters];
     try {
@@ -2274,6 +2297,20 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
     empty_unless_built.armed = false;
     return BK_OK;
 }
+
+#if BK_DEBUG_API
+/* test hook: the forward build's quad pass on a corner table of the caller's (blinky_hip_debug.h) */
+extern "C" int bk_debug_set_forward_corners(bk_ctx *ctx, const int32_t *xy, const uint8_t *ok, size_t ncorners)
+{
+    if (!ctx) return BK_E_INVALID;
+    ctx->clear_debug_corners();
+    if (!xy || !ok || !ncorners) return BK_OK;
+    ctx->dbg_corner_xy.assign(xy, xy + 2 * ncorners);
+    ctx->dbg_corner_ok.assign(ok, ok + ncorners);
+    ctx->dbg_corners_set = true;
+    return BK_OK;
+}
+#endif
 
 #if BK_DEBUG_API
 extern "C" int bk_debug_forward_tiles(bk_ctx *ctx, int *taken, int *total)

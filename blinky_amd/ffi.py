@@ -119,6 +119,7 @@ _SIGS = {
     "bk_debug_build_params": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "bk_debug_host_entries": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "bk_debug_host_corners": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "bk_debug_set_forward_corners": (_i, [_vp, _vp, _vp, _sz]),
     "bk_debug_xcd_of_workgroups": (_i, [_vp, C.POINTER(_i), _i]),
     "bk_debug_set_ablation": (_i, [_vp, _i]),
     "bk_debug_set_tile_shape": (_i, [_vp, _i]),
@@ -525,6 +526,18 @@ class Context:
         ok = np.empty(len(ids), np.uint8)
         self._chk(lib.bk_debug_host_corners(self._h, _ptr(ids), len(ids), _ptr(sx), _ptr(sy), _ptr(ok)))
         return sx, sy, ok
+
+    def set_forward_corners(self, xy=None, ok=None):
+        """hand the forward build's quad pass a corner table (bk_debug_set_forward_corners): xy int32 [ncorners, 2], ok uint8 [ncorners];
+        None clears it"""
+        if xy is None or ok is None:
+            self._chk(lib.bk_debug_set_forward_corners(self._h, None, None, 0))
+            return
+        xy = np.ascontiguousarray(xy, dtype=np.int32)
+        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        if xy.size != 2 * ok.size:
+            raise ValueError("set_forward_corners: xy must hold two coordinates per corner")
+        self._chk(lib.bk_debug_set_forward_corners(self._h, _ptr(xy), _ptr(ok), ok.size))
 
     def xcd_of_workgroups(self, n):
         out = (_i * n)()

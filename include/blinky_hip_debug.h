@@ -85,6 +85,17 @@ int         bk_debug_host_entries(bk_ctx *ctx, const uint32_t *ids, size_t n, ui
 /* the same for the texel corners of the forward build (corner number plate * (ps+1)^2 + j * (ps+1) + i): screen x, y, and
  * whether lens_forward gave a position */
 int         bk_debug_host_corners(bk_ctx *ctx, const uint32_t *ids, size_t n, int32_t *sx, int32_t *sy, uint8_t *ok);
+/* test hook: hand the forward build's QUAD PASS a texel-corner table.  xy = ncorners pairs of screen x, y, ok = ncorners flags
+ * ("lens_forward gave a position"), corner number (plate * (ps+1) + j) * (ps+1) + i as in bk_debug_host_corners; the library keeps a
+ * host copy, NULL or 0 clears it.  While a table is set, a forward-map build on the device copies it into its corner planes IN PLACE
+ * OF the corner pass (bk_forward_corners) - on the one-submission path and on the pass-by-pass one ("forward_careful") alike; no corner
+ * is flagged, the corner error is 0, and everything after it (key planes, bk_forward_tiles, the quad pass with its texel-ownership
+ * test, resolve, the counters) runs as it always does.  The lens only has to give the build a module and a scale (lens_width /
+ * lens_height and a lens_forward that returns x, y).  bk_build fails with BK_E_INVALID when ncorners is not
+ * plates * (platesize + 1)^2 at build time, and with BK_E_STATE (over an empty map) when a table is set and the build does not go
+ * through the device's forward passes - an inverse map, a host path; a device-less context cannot build at all.  bk_resize,
+ * bk_load_globe and bk_set_globe_plates clear the table. */
+int         bk_debug_set_forward_corners(bk_ctx *ctx, const int32_t *xy, const uint8_t *ok, size_t ncorners);
 /* evaluate a callback with the HOST interpreter, for diagnosing a script: which 0 = lens_inverse(x,y),
  * 1 = lens_forward(x,y,z), 2 = globe_plate(x,y,z); *nout = number of results, -1 for a single nil */
 int         bk_debug_eval(bk_ctx *ctx, int which, const double *args, int nargs, double out[8], int *nout);

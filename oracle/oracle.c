@@ -432,13 +432,15 @@ void ok_test_draw_quad(int W, int H, const int corners[8], unsigned char *mask)
 static int build_forward(ok_state *s)
 {
     int ps = s->platesize;
-    int *rowa = (int *)malloc((size_t)(ps + 1) * 2 * sizeof(int));
-    int *rowb = (int *)malloc((size_t)(ps + 1) * 2 * sizeof(int));
-    unsigned char *vala = (unsigned char *)malloc((size_t)ps + 1);
-    unsigned char *valb = (unsigned char *)malloc((size_t)ps + 1);
+    /* (zeroed: a nil corner's coordinates are never written, and the corner hook below copies whole rows) */
+    int *rowa = (int *)calloc((size_t)(ps + 1) * 2, sizeof(int));
+    int *rowb = (int *)calloc((size_t)(ps + 1) * 2, sizeof(int));
+    unsigned char *vala = (unsigned char *)calloc((size_t)ps + 1, 1);
+    unsigned char *valb = (unsigned char *)calloc((size_t)ps + 1, 1);
     int *top = rowa, *bot = rowb;
     unsigned char *topv = vala, *botv = valb;
     int plate, py, px, ok = 1;
+    const size_t n1 = (size_t)ps + 1;
 
     for (plate = 0; plate < s->numplates && ok; ++plate) {
         for (py = ps - 1; py >= 0 && ok; --py) {
@@ -486,6 +488,15 @@ static int build_forward(ok_state *s)
                 }
                 if (!ok) break;
             }
+            /* test hook: the two rows of corners as they stand now (row py + 1 of the table = this quad row's lower points) */
+            if (s->corner_xy) {
+                memcpy(s->corner_xy + 2 * (((size_t)plate * n1 + (size_t)py) * n1), top, n1 * 2 * sizeof(int));
+                memcpy(s->corner_xy + 2 * (((size_t)plate * n1 + (size_t)py + 1) * n1), bot, n1 * 2 * sizeof(int));
+            }
+            if (s->corner_ok) {
+                memcpy(s->corner_ok + ((size_t)plate * n1 + (size_t)py) * n1, topv, n1);
+                memcpy(s->corner_ok + ((size_t)plate * n1 + (size_t)py + 1) * n1, botv, n1);
+            }
             {                                                             /* :2189 draw quads */
                 double v = ((double)py) / ps;
                 for (px = 0; px < ps; ++px) {
@@ -505,6 +516,50 @@ static int build_forward(ok_state *s)
     }
     free(rowa); free(rowb); free(vala); free(valb);
     return ok;
+}
+
+/* TEST HOOK: build_forward's quad loop (:2189-2202) driven by a given corner table: plates ascending, py descending, px ascending,
+ * the ownership test, the four corners' flags, draw_quad - the lines above, with `top` / `bot` pointing into the table. */
+void ok_forward_from_corners(ok_state *s, const int *xy, const uint8_t *okc)
+{
+    const int ps = s->platesize;
+    const size_t n1 = (size_t)ps + 1, area = (size_t)s->width_px * (size_t)s->height_px;
+    size_t i;
+    int plate, py, px;
+    for (i = 0; i < area; ++i) s->offsets[i] = OK_NULL_OFFSET;            /* :731 */
+    memset(s->tints, 255, area);                                          /* :732 */
+    for (plate = 0; plate < s->numplates; plate++) s->plates[plate].display = 0;   /* :2383 */
+    for (plate = 0; plate < s->numplates; ++plate) {
+        for (py = ps - 1; py >= 0; --py) {
+            const int *top = xy + 2 * (((size_t)plate * n1 + (size_t)py) * n1), *bot = top + 2 * n1;
+            const uint8_t *topv = okc + ((size_t)plate * n1 + (size_t)py) * n1, *botv = topv + n1;
+            double v = ((double)py) / ps;
+            for (px = 0; px < ps; ++px) {
+                double u = ((double)px) / ps;
+                float ray[3];
+                int index = 2 * px;
+                ok_plate_uv_to_ray(s, plate, u, v, ray);
+                if (plate != ray_to_plate_index(s, ray))                  /* :2196 */
+                    continue;
+                if (!(topv[px] && topv[px + 1] && botv[px] && botv[px + 1]))
+                    continue;
+                draw_quad(s, &top[index], &top[index + 2], &bot[index], &bot[index + 2], plate, px, py);
+            }
+        }
+    }
+}
+
+void ok_texel_owners(const ok_state *s, uint8_t *own)
+{
+    const int ps = s->platesize;
+    int plate, py, px;
+    for (plate = 0; plate < s->numplates; ++plate)
+        for (py = 0; py < ps; ++py)
+            for (px = 0; px < ps; ++px) {
+                float ray[3];
+                ok_plate_uv_to_ray(s, plate, ((double)px) / ps, ((double)py) / ps, ray);     /* :2193-2195 */
+                own[((size_t)plate * ps + py) * ps + px] = (uint8_t)(plate == ray_to_plate_index(s, ray));
+            }
 }
 
 /* ---- create_lensmap (fisheye.c:2367-2397) + the clears of F_RenderView:731-732 */

@@ -79,6 +79,10 @@ typedef struct {
     /* outputs: offset = ptr - globe.pixels, OK_NULL_OFFSET for NULL; tints */
     uint32_t *offsets;
     uint8_t *tints;
+    /* test hook (either may be NULL): the forward build records what uv_to_screen gave for every texel corner,
+     * [numplates][ps+1][ps+1] with corner (i, j) = (u, v) = ((i-0.5)/ps, (j-0.5)/ps): x, y pairs and "gave a position" */
+    int *corner_xy;
+    uint8_t *corner_ok;
 } ok_state;
 
 /* pure converters (fisheye.c:1184-1214) */
@@ -101,6 +105,12 @@ int  ok_calc_zoom(ok_state *s);
  * Caller provides offsets[W*H], tints[W*H]; they are cleared here the way
  * F_RenderView does (fisheye.c:731-732).  Returns 1 ok, 0 aborted. */
 int  ok_create_lensmap(ok_state *s);
+/* TEST HOOK: the quad loop of the forward build (fisheye.c:2189-2202) over a GIVEN table of texel corners instead of uv_to_screen's:
+ * xy / ok laid out as ok_state::corner_xy / corner_ok.  Needs the globe, width_px / height_px / platesize, the rubix grid and
+ * offsets / tints, which it clears first as ok_create_lensmap does; no lens, no zoom.  plates[].display is set as the build sets it. */
+void ok_forward_from_corners(ok_state *s, const int *xy, const uint8_t *ok);
+/* TEST HOOK: own[(plate * ps + py) * ps + px] = 1 where the ray through texel (px, py) selects its own plate (:2193-2196) */
+void ok_texel_owners(const ok_state *s, uint8_t *own);
 /* same, rows [y0,y1) only of the inverse map (used for stripe tests) */
 int  ok_build_inverse_rows(ok_state *s, int y0, int y1);
 

@@ -9,21 +9,64 @@
 #include <string.h>
 
 /* build a lensmap for (globe, lens, zoom) at W x H with the given rubix grid.
- * returns 1 if built; fills offsets/tints (W*H), display[6], scale, numplates, map_type */
-int okpy_lensmap(const char *globe, const char *lens, const char *zoomcmd, int W, int H,
-                 int numcells, double cell, double pad,
-                 uint32_t *offsets, uint8_t *tints, int *display, double *scale,
-                 int *numplates, int *map_type)
+ * returns 1 if built; fills offsets/tints (W*H), display[6], scale, numplates, map_type, and - where the pointers are given and the
+ * lens is a forward one - the texel-corner table the build computed (ok_state::corner_xy / corner_ok; 6 * (ps+1)^2 entries of room) */
+int okpy_lensmap_corners(const char *globe, const char *lens, const char *zoomcmd, int W, int H,
+                         int numcells, double cell, double pad,
+                         uint32_t *offsets, uint8_t *tints, int *display, double *scale,
+                         int *numplates, int *map_type, int *corner_xy, uint8_t *corner_ok)
 {
     ok_state s;
     int i, ok;
     if (!ok_configure(&s, globe, lens, zoomcmd, W, H)) return -1;
     s.rubix_numcells = numcells; s.rubix_cell = cell; s.rubix_pad = pad;
     s.offsets = offsets; s.tints = tints;
+    s.corner_xy = corner_xy; s.corner_ok = corner_ok;
     ok = ok_create_lensmap(&s);
     for (i = 0; i < OK_MAX_PLATES; ++i) display[i] = i < s.numplates ? s.plates[i].display : 0;
     *scale = s.scale; *numplates = s.numplates; *map_type = s.map_type;
     return ok;
+}
+
+/* the same without the corner table (the entry's arguments as they have always been: callers bound to them keep working) */
+int okpy_lensmap(const char *globe, const char *lens, const char *zoomcmd, int W, int H,
+                 int numcells, double cell, double pad,
+                 uint32_t *offsets, uint8_t *tints, int *display, double *scale,
+                 int *numplates, int *map_type)
+{
+    return okpy_lensmap_corners(globe, lens, zoomcmd, W, H, numcells, cell, pad, offsets, tints, display, scale, numplates, map_type, NULL, NULL);
+}
+
+/* the forward build's quad loop over a given corner table (ok_forward_from_corners): globe by name, ps = min(W, H).
+ * returns 1, or -1 for an unknown globe or one with a globe_plate script (the loop would need the script) */
+int okpy_forward_from_corners(const char *globe, int W, int H, int numcells, double cell, double pad,
+                              const int *xy, const uint8_t *okc, uint32_t *offsets, uint8_t *tints, int *display, int *numplates)
+{
+    ok_state s;
+    int i;
+    memset(&s, 0, sizeof s);
+    ok_default_host(&s);
+    if (!ok_use_globe(&s, globe) || s.globe_plate) return -1;
+    s.rubix_numcells = numcells; s.rubix_cell = cell; s.rubix_pad = pad;
+    s.width_px = W; s.height_px = H;
+    s.platesize = W < H ? W : H;                                         /* fisheye.c:707 */
+    s.offsets = offsets; s.tints = tints;
+    ok_forward_from_corners(&s, xy, okc);
+    for (i = 0; i < OK_MAX_PLATES; ++i) display[i] = i < s.numplates ? s.plates[i].display : 0;
+    *numplates = s.numplates;
+    return 1;
+}
+
+/* which texels of a globe's plates own their ray (fisheye.c:2193-2196): own[numplates][ps][ps]; returns numplates or -1 */
+int okpy_texel_owners(const char *globe, int ps, uint8_t *own)
+{
+    ok_state s;
+    memset(&s, 0, sizeof s);
+    ok_default_host(&s);
+    if (!ok_use_globe(&s, globe) || s.globe_plate) return -1;
+    s.platesize = ps;
+    ok_texel_owners(&s, own);
+    return s.numplates;
 }
 
 /* plates of a transliterated globe, in LUA_load_globe's float form (13 floats per plate:

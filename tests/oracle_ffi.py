@@ -26,6 +26,12 @@ _o.ok_lcg_fill_plate.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int]
 _o.okpy_lensmap.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double,
                             C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double),
                             C.POINTER(C.c_int), C.POINTER(C.c_int)]
+for _lib in (_o, _ob):
+    _lib.okpy_lensmap_corners.argtypes = _o.okpy_lensmap.argtypes + [C.c_void_p, C.c_void_p]
+_o.okpy_forward_from_corners.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+_o.okpy_texel_owners.argtypes = [C.c_char_p, C.c_int, C.c_void_p]
+_o.ok_test_draw_quad.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
 _o.okpy_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                           C.c_int, C.c_int, C.c_int, C.c_void_p]
 _o.okpy_palmap.argtypes = [C.c_void_p, C.c_void_p]
@@ -53,19 +59,65 @@ class Lensmap:
         return int((self.offsets != NULL).sum())
 
 
-def lensmap(globe, lens, zoom, W, H, grid=(10, 4.0, 1.0), portable=False):
+def lensmap(globe, lens, zoom, W, H, grid=(10, 4.0, 1.0), portable=False, corners=False):
     """Oracle lensmap for 'f_globe G; f_lens L; zoom' at WxH (zoom None = the lens' onload).
-    portable=True: the liboracle_bkm.so build (every libm call = the GPU kernels' bkm.h function)."""
+    portable=True: the liboracle_bkm.so build (every libm call = the GPU kernels' bkm.h function).
+    corners=True: the Lensmap also carries the texel-corner table a forward build computed, corner_xy int32 [n, 2] and
+    corner_ok uint8 [n], n = numplates * (ps+1)^2 in bk_debug_host_corners' numbering (None for an inverse lens or a failed build)."""
     off = np.empty(W * H, np.uint32)
     tin = np.empty(W * H, np.uint8)
     disp = (C.c_int * 6)()
     scale, npl, mt = C.c_double(), C.c_int(), C.c_int()
-    rc = (_ob if portable else _o).okpy_lensmap(globe.encode(), lens.encode(), zoom.encode() if zoom else None, W, H,
-                         int(grid[0]), float(grid[1]), float(grid[2]), _p(off), _p(tin), disp,
-                         C.byref(scale), C.byref(npl), C.byref(mt))
+    n1 = min(W, H) + 1
+    cxy = np.zeros((6 * n1 * n1, 2), np.int32) if corners else None
+    cok = np.full(6 * n1 * n1, 255, np.uint8) if corners else None
+    lib = _ob if portable else _o
+    args = (globe.encode(), lens.encode(), zoom.encode() if zoom else None, W, H, int(grid[0]), float(grid[1]), float(grid[2]),
+            _p(off), _p(tin), disp, C.byref(scale), C.byref(npl), C.byref(mt))
+    rc = lib.okpy_lensmap_corners(*args, _p(cxy), _p(cok)) if corners else lib.okpy_lensmap(*args)
     if rc < 0:
         raise KeyError(f"oracle has no transliteration of {globe}/{lens}")
-    return Lensmap(W, H, off, tin, list(disp)[: npl.value], scale.value, npl.value, mt.value, rc == 1)
+    lm = Lensmap(W, H, off, tin, list(disp)[: npl.value], scale.value, npl.value, mt.value, rc == 1)
+    lm.corner_xy = lm.corner_ok = None
+    if corners and rc == 1 and mt.value == 2:
+        lm.corner_xy, lm.corner_ok = cxy[: npl.value * n1 * n1], cok[: npl.value * n1 * n1]
+    return lm
+
+
+def forward_from_corners(globe, W, H, grid, xy, ok):
+    """The oracle's forward quad loop (fisheye.c:2189-2202) over a GIVEN corner table (ok_forward_from_corners): a Lensmap with
+    offsets, tints and display; ps = min(W, H), xy int32 [n, 2], ok uint8 [n], n = numplates * (ps+1)^2."""
+    xy = np.ascontiguousarray(xy, np.int32)
+    ok = np.ascontiguousarray(ok, np.uint8)
+    n1 = min(W, H) + 1
+    nplates = len(globe_plates(globe))
+    assert ok.size == nplates * n1 * n1 and xy.size == 2 * ok.size, (ok.size, xy.size, nplates, n1)
+    off = np.empty(W * H, np.uint32)
+    tin = np.empty(W * H, np.uint8)
+    disp = (C.c_int * 6)()
+    npl = C.c_int()
+    rc = _o.okpy_forward_from_corners(globe.encode(), W, H, int(grid[0]), float(grid[1]), float(grid[2]), _p(xy), _p(ok),
+                                      _p(off), _p(tin), disp, C.byref(npl))
+    if rc < 0:
+        raise KeyError(globe)
+    return Lensmap(W, H, off, tin, list(disp)[: npl.value], None, npl.value, 2, True)
+
+
+def texel_owners(globe, ps):
+    """uint8 [numplates, ps, ps]: 1 where the ray through texel (px, py) selects its own plate (fisheye.c:2193-2196)"""
+    own = np.zeros((6, ps, ps), np.uint8)
+    n = _o.okpy_texel_owners(globe.encode(), ps, _p(own))
+    if n < 0:
+        raise KeyError(globe)
+    return own[:n]
+
+
+def draw_quad_mask(W, H, corners):
+    """ok_test_draw_quad: the W x H mask of pixels the oracle's draw_quad writes for corners (tl, tr, bl, br: x, y each)"""
+    c = np.ascontiguousarray(corners, np.int32).reshape(8)
+    mask = np.zeros(W * H, np.uint8)
+    _o.ok_test_draw_quad(W, H, _p(c), _p(mask))
+    return mask
 
 
 def globe_plates(name):
