@@ -154,6 +154,7 @@ extern "C" void bk_destroy(bk_ctx *ctx)
     hipFree(ctx->d_plate_stage);
     hipFree(ctx->d_rgba_stage);
     hipFree(ctx->d_pal);
+    hipFree(ctx->d_lut_rgba);
     hipFree(ctx->d_display);
     hipFree(ctx->d_flag_list);
     for (void *q : ctx->fwd_scratch) hipFree(q);
@@ -694,22 +695,56 @@ extern "C" int bk_apply_device(bk_ctx *ctx, int frame0, int nframes, void *dst_d
     return bk::launch_apply(ctx, frame0, nframes, first, dst_pitch, frame_stride, rubix_on);
 }
 
+// what bk_apply_rgba_device and bk_apply_rgba_tinted_device check alike; `who` names the entry point in the message
+static int rgba_apply_args(bk_ctx *ctx, const char *who, int globe0, int nframes, const void *dst_dev, int dst_pitch, size_t frame_stride, int x0, int y0)
+{
+    if (ctx->device < 0) return ctx->fail(BK_E_STATE, "%s: this context was created without a device (BK_DEVICE_NONE)", who);
+    if (!ctx->lensmap_valid) return ctx->fail(BK_E_STATE, "%s: no lensmap (bk_build / bk_set_lensmap first)", who);
+    if (x0 < 0 || y0 < 0 || globe0 < 0 || nframes < 1 || (long long)dst_pitch < 4ll * ((long long)ctx->W + x0))
+        return ctx->fail(BK_E_INVALID, "%s: bad pitch/origin/frames", who);
+    if (((uintptr_t)dst_dev | (uintptr_t)dst_pitch | (uintptr_t)frame_stride) & 3u)
+        return ctx->fail(BK_E_INVALID, "%s: dst, pitch and frame stride must be multiples of 4 bytes", who);
+    if (ctx->nframes < 4) return ctx->fail(BK_E_STATE, "%s: a truecolour globe is four ring slots (bk_set_frames(4 * globes))", who);
+    if (ctx->apply_variant == 0) return ctx->fail(BK_E_STATE, "%s: the truecolour apply is the staged variant (bk_set_apply_variant 2 / -1)", who);
+    return BK_OK;
+}
+
 // truecolour frames: frame f from truecolour globe (globe0 + f) % (ring slots / 4), 4 bytes per pixel (bk_apply_rgba.inc)
 extern "C" int bk_apply_rgba_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch, size_t frame_stride, int x0, int y0)
 {
     if (!ctx || !dst_dev) return BK_E_INVALID;
-    if (ctx->device < 0) return ctx->fail(BK_E_STATE, "bk_apply_rgba_device: this context was created without a device (BK_DEVICE_NONE)");
-    if (!ctx->lensmap_valid) return ctx->fail(BK_E_STATE, "bk_apply_rgba_device: no lensmap (bk_build / bk_set_lensmap first)");
-    if (x0 < 0 || y0 < 0 || globe0 < 0 || nframes < 1 || (long long)dst_pitch < 4ll * ((long long)ctx->W + x0))
-        return ctx->fail(BK_E_INVALID, "bk_apply_rgba_device: bad pitch/origin/frames");
-    if (((uintptr_t)dst_dev | (uintptr_t)dst_pitch | (uintptr_t)frame_stride) & 3u)
-        return ctx->fail(BK_E_INVALID, "bk_apply_rgba_device: dst, pitch and frame stride must be multiples of 4 bytes");
-    if (ctx->nframes < 4) return ctx->fail(BK_E_STATE, "bk_apply_rgba_device: a truecolour globe is four ring slots (bk_set_frames(4 * globes))");
-    if (ctx->apply_variant == 0) return ctx->fail(BK_E_STATE, "bk_apply_rgba_device: the truecolour apply is the staged variant (bk_set_apply_variant 2 / -1)");
+    if (int r = rgba_apply_args(ctx, "bk_apply_rgba_device", globe0, nframes, dst_dev, dst_pitch, frame_stride, x0, y0)) return r;
     if (int r = ensure_device(ctx)) return r;                // (ends a resident session, as bk_apply_device)
     bk::Range range("bk_apply_rgba_device");
     uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
     return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride);
+}
+
+// the device copy of a truecolour launch's byte LUTs, kept as upload_pal keeps the 8-bit palette: while the bytes AND the stream are
+// the same.  A buffer of its own - ctx->d_pal and its cache stay what the last 8-bit rubix launch made them.
+static int upload_lut_rgba(bk_ctx *ctx, const uint8_t lut[4][BK_MAX_PLATES][256])
+{
+    if (!ctx->d_lut_rgba) BK_HIP(ctx, hipMalloc((void **)&ctx->d_lut_rgba, sizeof ctx->lut_rgba_cache));
+    if (ctx->lut_rgba_cached && ctx->lut_rgba_stream == ctx->stream && memcmp(ctx->lut_rgba_cache, lut, sizeof ctx->lut_rgba_cache) == 0) return BK_OK;
+    ctx->lut_rgba_cached = false;
+    BK_HIP(ctx, hipMemcpyAsync(ctx->d_lut_rgba, lut, sizeof ctx->lut_rgba_cache, hipMemcpyHostToDevice, ctx->stream));
+    memcpy(ctx->lut_rgba_cache, lut, sizeof ctx->lut_rgba_cache);
+    ctx->lut_rgba_stream = ctx->stream;
+    ctx->lut_rgba_cached = true;
+    return BK_OK;
+}
+
+// bk_apply_rgba_device with rubix: byte c of a mapped pixel of tint t < BK_MAX_PLATES leaves as lut[c][t][v]
+extern "C" int bk_apply_rgba_tinted_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch, size_t frame_stride, int x0, int y0,
+                                           const uint8_t lut[4][BK_MAX_PLATES][256])
+{
+    if (!ctx || !dst_dev || !lut) return BK_E_INVALID;
+    if (int r = rgba_apply_args(ctx, "bk_apply_rgba_tinted_device", globe0, nframes, dst_dev, dst_pitch, frame_stride, x0, y0)) return r;
+    if (int r = ensure_device(ctx)) return r;
+    bk::Range range("bk_apply_rgba_tinted_device");
+    if (int r = upload_lut_rgba(ctx, lut)) return r;
+    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
+    return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride, ctx->d_lut_rgba);
 }
 
 // ---- resident single-frame apply (bk_apply_resident.inc) ------------------------------------------------------------
@@ -955,19 +990,34 @@ static int closest_pal_index(const uint8_t *basepal, int r, int g, int b)
     return besti;
 }
 
+static const int bk_rubix_tint[BK_MAX_PLATES][3] = {{255, 255, 255}, {0, 0, 255}, {255, 0, 0},
+                                                    {255, 255, 0}, {255, 0, 255}, {0, 255, 255}};   // fisheye.c:866-886
+static const int bk_rubix_percent = 256 / 6;                                                        // fisheye.c:860
+
+static inline int rubix_blend(int v, int tint)
+{
+    v += bk_rubix_percent * (tint - v) >> 8;                                                  // fisheye.c:895
+    return v < 0 ? 0 : v > 255 ? 255 : v;                                                      // fisheye.c:899
+}
+
 extern "C" void bk_create_palmap(const uint8_t *basepal, uint8_t pal_out[BK_MAX_PLATES][256])
 {
-    static const int tint[BK_MAX_PLATES][3] = {{255, 255, 255}, {0, 0, 255}, {255, 0, 0},
-                                               {255, 255, 0}, {255, 0, 255}, {0, 255, 255}};   // fisheye.c:866-886
-    const int percent = 256 / 6;
     for (int j = 0; j < BK_MAX_PLATES; ++j)
         for (int i = 0; i < 256; ++i) {
             int c[3];
-            for (int k = 0; k < 3; ++k) {
-                int v = basepal[3 * i + k];
-                v += percent * (tint[j][k] - v) >> 8;                                         // fisheye.c:895
-                c[k] = v < 0 ? 0 : v > 255 ? 255 : v;
-            }
+            for (int k = 0; k < 3; ++k) c[k] = rubix_blend(basepal[3 * i + k], bk_rubix_tint[j][k]);
             pal_out[j][i] = (uint8_t)closest_pal_index(basepal, c[0], c[1], c[2]);
         }
+}
+
+// the same blend for truecolour texels, where nothing is quantised afterwards: a byte -> byte table per (byte of the texel, plate)
+extern "C" void bk_create_tintmap_rgba(const int channel_of_byte[4], uint8_t lut_out[4][BK_MAX_PLATES][256])
+{
+    if (!channel_of_byte || !lut_out) return;
+    for (int c = 0; c < 4; ++c) {
+        const int ch = channel_of_byte[c];
+        for (int j = 0; j < BK_MAX_PLATES; ++j)
+            for (int v = 0; v < 256; ++v)
+                lut_out[c][j][v] = (uint8_t)(ch >= 0 && ch <= 2 ? rubix_blend(v, bk_rubix_tint[j][ch]) : v);    // (alpha: as it is)
+    }
 }

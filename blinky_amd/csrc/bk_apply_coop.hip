@@ -1437,7 +1437,9 @@ static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, ui
     //  slower - 4K panini at 128x16: 12.0 -> 18.3 us single frame, 4.5 -> 6.4 us/frame x16: 77-96 VGPRs against 67 - and the
     //  whole-globe lenses it was meant for have larger blocks.  What separates mercator's 16.5 us from hammer's 11.5 is not per-block
     //  latency but the quantisation of rounds: 4050 live blocks on 1792 resident places are 2.26 rounds and take 3.)
-#define BK_APPLY_K(KERNEL, RBX, N) hipLaunchKernelGGL((KERNEL<RBX, N>), grid, dim3(256), shmem, ctx->stream, cm->d_hdr, cm->d_list, cm->d_idx, \
+    // (a 64 KiB staging buffer with the palette behind it is more dynamic LDS than a kernel gets unasked)
+#define BK_APPLY_K(KERNEL, RBX, N) if (shmem > 65536) BK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL<RBX, N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
+                                   hipLaunchKernelGGL((KERNEL<RBX, N>), grid, dim3(256), shmem, ctx->stream, cm->d_hdr, cm->d_list, cm->d_idx, \
                                            ctx->d_tints, ctx->d_offsets, ctx->d_globe, ctx->globe_stride(), ctx->nframes, frame0, dst,    \
                                            dst_pitch, frame_stride, ctx->W, rows, blocks_x, nblocks, nframes, fchunk, lds_buf,           \
                                            ctx->d_pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap)
@@ -1449,9 +1451,9 @@ static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, ui
                                            ctx->d_tints, ctx->d_offsets, ctx->d_globe, ctx->globe_stride(), ctx->nframes, frame0, dst,    \
                                            dst_pitch, frame_stride, ctx->W, rows, blocks_x, nblocks, nframes, fchunk, lds_buf,           \
                                            ctx->d_pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap)
-#define BK_APPLY(N) do { if (once && dma) BK_APPLY_KD(N); else if (once) BK_APPLY_K(apply_coop_once_kernel, false, N);                 \
-                         else if (wideq) BK_APPLY_KW(N); else BK_APPLY_K(apply_coop_kernel, false, N); } while (0)
-#define BK_APPLY_R(N) do { if (once) BK_APPLY_K(apply_coop_once_kernel, true, N); else BK_APPLY_K(apply_coop_kernel, true, N); } while (0)
+#define BK_APPLY(N) do { if (once && dma) BK_APPLY_KD(N); else if (once) { BK_APPLY_K(apply_coop_once_kernel, false, N); }             \
+                         else if (wideq) BK_APPLY_KW(N); else { BK_APPLY_K(apply_coop_kernel, false, N); } } while (0)
+#define BK_APPLY_R(N) do { if (once) { BK_APPLY_K(apply_coop_once_kernel, true, N); } else { BK_APPLY_K(apply_coop_kernel, true, N); } } while (0)
     if (rubix_on) { if (cm->rg == 1) BK_APPLY_R(1); else if (cm->rg == 2) BK_APPLY_R(2); else BK_APPLY_R(4); }
     else { if (cm->rg == 1) BK_APPLY(1); else if (cm->rg == 2) BK_APPLY(2); else BK_APPLY(4); }
 #undef BK_APPLY_R

@@ -15,9 +15,29 @@
 //  profiles/rgba_apply.txt, which also has what consecutive pixels per lane cost).
 // One block per workgroup, the PLAIN block map as ensure_coopmap compiles and tunes it for a launch of 4 * nframes planes; a block
 // visit serves max(1, fchunk / 4) truecolour frames, i.e. the block map is read once per about 8 planes as in the 8-bit batch
-// launch.  No rubix, no strided / persistent / LDS-DMA form.
+// launch.  No strided / persistent / LDS-DMA form.
 // Blocks the staging does not serve - a chunk list larger than the launch's staging buffer, CF_SLOW blocks without a list - gather
 // straight from the lensmap: four byte loads and one dword store per mapped pixel (rare on real lenses; no multi-pass form).
+//
+// RUBIX (bk_apply_rgba_tinted_device, apply_coop_rgba_tinted_kernel<RG>): a tint on truecolour texels is a byte -> byte table per (byte
+// plane, plate) - uint8 lut[4][6][256] - so plane c of a tinted frame is the 8-bit rubix gather of slot 4g + c through LUT c: the launch
+// runs over the TINTED block map (CoopMap::tinted: a chunk listed once per tint class, the class in the entry's low three bits), loads
+// from entry & ~15 and sends the 16 staged bytes through row class - 1 of the plane's LUT on their way to LDS (bk_rgba_tint_chunk) - the
+// four register-held chunks and the rounds above 1024 chunks alike.  Everything behind the barrier is the plain kernel's.
+// Where the LUTs live: ONE plane's 1.5 KiB in LDS behind the staging buffer, not all four (6 KiB).  Plane c + 1's 384 dwords are
+// requested in front of plane c + 1's chunk loads - right behind the barrier that ends plane c's staging pass, the last reader of LUT c -
+// ride in two registers through plane c's gather and are committed in front of the barrier that ends it (the BK_COOP_PROLOGUE /
+// BK_COOP_PAL_COMMIT pattern: request early, commit late; no barrier added per plane).  LDS per workgroup is then what the 8-bit tinted
+// kernel takes, staging buffer + 1.5 KiB; four LUTs would take a CU's 160 KiB from 8 workgroups to 6 at 4K panini's 18 KiB and from
+// 6 to 5 at hammer's 25 KiB.  As built (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; no scratch in any of them):
+//     plain  RG 1 / 2 / 4: 52 / 60 / 77 VGPRs = 8 / 7 / 6 waves per SIMD (a workgroup is one wave per SIMD: as many workgroups per CU)
+//     tinted RG 1 / 2 / 4: 73 / 79 / 94 VGPRs = 6 / 6 / 5 waves per SIMD; LDS 19.5 KiB at 4K panini (RG 4), 26.5 KiB at 4K hammer (RG 2):
+//     8 and 6 workgroups per CU by LDS - in the tinted kernel the REGISTERS decide, 5 and 6.
+// Blocks without staging look the pixel's tint up in the lensmap's tint plane and its four bytes in the LUTs in device memory.
+// Measured (tools/bench_rgba.py --tint, profiles/rgba_tint_apply.txt; A' = the 64-frame 8-bit rubix launch over the same slots through
+// the same palette, B = the plain truecolour launch): 4K hammer 440.9 us against A' 445.0 and B 400.3; 4K panini 270.4 us against
+// A' 232.9 and B 212.4 - there the target (A' + its spread) is MISSED by 16 %: the same look-ups per chunk as A', hidden by 5 workgroups
+// per CU where the 8-bit tinted kernel (64 VGPRs) has 8.  Asking for 6 waves (amdgpu_waves_per_eu) spills 60 bytes per lane at RG = 4.
 
 // the lane's 4 pixels of row group r as whole dwords: P[c] holds byte c of pixels 0..3 -> px[k] holds bytes 0..3 of pixel k
 __device__ __forceinline__ void bk_rgba_transpose(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t px[4])
@@ -33,14 +53,36 @@ __device__ __forceinline__ void bk_rgba_transpose(uint32_t p0, uint32_t p1, uint
     px[3] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
 }
 
+// bk_tint_chunk for this kernel: the same sixteen look-ups, TGROUP words (4 * TGROUP byte reads and their addresses) in flight at a
+// time - all sixteen at once put RG = 2 at 82 VGPRs (5 waves per SIMD); two words at a time: 79 (6)
+template <int TGROUP>
+__device__ __forceinline__ uint4 bk_rgba_tint_chunk(uint4 q, uint32_t e, const uint8_t *pal_s)
+{
+    const uint32_t cls = e & 7u;
+    if (cls) {
+        const uint8_t *row = pal_s + (cls - 1u) * 256u;
+        uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            w[i] = (uint32_t)row[w[i] & 0xFFu] | ((uint32_t)row[(w[i] >> 8) & 0xFFu] << 8) | ((uint32_t)row[(w[i] >> 16) & 0xFFu] << 16) |
+                   ((uint32_t)row[w[i] >> 24] << 24);
+            if (i % TGROUP == TGROUP - 1) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
+        }
+        q = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    return q;
+}
+
 // truecolour frames of one staged block: four planes per frame through the one staging buffer, plane c + 1's chunks requested before
 // plane c's gather (coop_frames does the same from frame to frame)
-template <int NQ, int RG>
+// RUBIX: `blist` / s0..s3 are entries of a TINTED block map (class in the low bits); pal_s = the 1.5 KiB behind the staging buffer that
+// hold the LUT of the plane being staged, lut = the four planes' LUTs in device memory (see the head comment)
+template <int NQ, int RG, bool RUBIX>
 __device__ __forceinline__ void rgba_frames(const uint8_t *__restrict__ globe, size_t globe_stride, int tglobes, int globe0, int f_begin,
                                             int f_end, uint8_t *__restrict__ dst, int dst_pitch, size_t frame_stride, uint8_t *buf,
                                             const uint32_t *__restrict__ blist, uint32_t nchunks, uint32_t s0, uint32_t s1, uint32_t s2,
                                             uint32_t s3, bool k0, bool k1, bool k2, bool k3, const CoopIdx<RG> ix, bool fast_store,
-                                            bool tile_empty, int row0, int xb, int cx)
+                                            bool tile_empty, int row0, int xb, int cx, const uint8_t *__restrict__ lut, uint8_t *pal_s)
 {
     // ix.iw[r] = the LDS addresses of the row's four-pixel group r * LPR + cx (rgba_load_idx); xb = the block's first pixel column
     constexpr int LPR = 32 / RG;
@@ -49,22 +91,48 @@ __device__ __forceinline__ void rgba_frames(const uint8_t *__restrict__ globe, s
 #define BK_RGBA_LOADS(F, C)                                                                    \
     do {                                                                                       \
         const uint8_t *gl_ = BK_RGBA_PLANE(F, C);                                              \
-        q0 = *reinterpret_cast<const uint4 *>(gl_ + s0);                                       \
-        if (NQ > 1) q1 = *reinterpret_cast<const uint4 *>(gl_ + s1);                           \
-        if (NQ > 2) q2 = *reinterpret_cast<const uint4 *>(gl_ + s2);                           \
-        if (NQ > 3) q3 = *reinterpret_cast<const uint4 *>(gl_ + s3);                           \
+        q0 = *reinterpret_cast<const uint4 *>(gl_ + BK_CHUNK_OFF(s0));                         \
+        if (NQ > 1) q1 = *reinterpret_cast<const uint4 *>(gl_ + BK_CHUNK_OFF(s1));             \
+        if (NQ > 2) q2 = *reinterpret_cast<const uint4 *>(gl_ + BK_CHUNK_OFF(s2));             \
+        if (NQ > 3) q3 = *reinterpret_cast<const uint4 *>(gl_ + BK_CHUNK_OFF(s3));             \
     } while (0)
+    // RUBIX: plane C's LUT - 384 dwords, one and a half per thread - is REQUESTED in front of the plane's chunk loads and COMMITTED to
+    // pal_s behind the previous plane's gather, where every wave is past the barrier that ends the staging pass which read the LUT before it
+    uint32_t pal_r0 = 0, pal_r1 = 0;
+#define BK_RGBA_LUT_REQUEST(C)                                                                 \
+    do {                                                                                       \
+        if (RUBIX) {                                                                           \
+            const uint32_t *l_ = reinterpret_cast<const uint32_t *>(lut + (C) * BK_PAL_BYTES); \
+            pal_r0 = l_[threadIdx.x];                                                          \
+            if (threadIdx.x < BK_PAL_BYTES / 4 - 256) pal_r1 = l_[256 + threadIdx.x];          \
+        }                                                                                      \
+    } while (0)
+#define BK_RGBA_LUT_COMMIT()                                                                   \
+    do {                                                                                       \
+        if (RUBIX) {                                                                           \
+            reinterpret_cast<uint32_t *>(pal_s)[threadIdx.x] = pal_r0;                         \
+            if (threadIdx.x < BK_PAL_BYTES / 4 - 256) reinterpret_cast<uint32_t *>(pal_s)[256 + threadIdx.x] = pal_r1; \
+        }                                                                                      \
+    } while (0)
+#define BK_RGBA_VAL(Q_, E_) (RUBIX ? bk_rgba_tint_chunk<2>((Q_), (E_), pal_s) : (Q_))
 #define BK_RGBA_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")      /* LDS traffic only: BK_LDS_BARRIER */
     uint8_t *mine = buf + threadIdx.x * 16u;
-    if (f_begin < f_end) BK_RGBA_LOADS(f_begin, 0);
+    if (f_begin < f_end) {
+        BK_RGBA_LUT_REQUEST(0);
+        BK_RGBA_LOADS(f_begin, 0);
+        if (RUBIX) {
+            BK_RGBA_LUT_COMMIT();
+            BK_RGBA_BARRIER();                // plane 0's LUT is in pal_s
+        }
+    }
     for (int f = f_begin; f < f_end; ++f) {
         uint32_t acc[4][RG];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            if (k0) *reinterpret_cast<uint4 *>(mine) = q0;
-            if (NQ > 1 && k1) *reinterpret_cast<uint4 *>(mine + 4096) = q1;
-            if (NQ > 2 && k2) *reinterpret_cast<uint4 *>(mine + 8192) = q2;
-            if (NQ > 3 && k3) *reinterpret_cast<uint4 *>(mine + 12288) = q3;
+            if (k0) *reinterpret_cast<uint4 *>(mine) = BK_RGBA_VAL(q0, s0);
+            if (NQ > 1 && k1) *reinterpret_cast<uint4 *>(mine + 4096) = BK_RGBA_VAL(q1, s1);
+            if (NQ > 2 && k2) *reinterpret_cast<uint4 *>(mine + 8192) = BK_RGBA_VAL(q2, s2);
+            if (NQ > 3 && k3) *reinterpret_cast<uint4 *>(mine + 12288) = BK_RGBA_VAL(q3, s3);
             if (NQ == 4) {
                 const uint8_t *gl = BK_RGBA_PLANE(f, c);
                 for (uint32_t c0 = 1024; c0 < nchunks; c0 += 1024) {      // blocks above what the registers hold: rounds of four loads
@@ -72,20 +140,21 @@ __device__ __forceinline__ void rgba_frames(const uint8_t *__restrict__ globe, s
                     const bool m0 = n < nchunks, m1 = n + 256u < nchunks, m2 = n + 512u < nchunks, m3 = n + 768u < nchunks;
                     const uint32_t a0 = m0 ? blist[n] : 0u, a1 = m1 ? blist[n + 256u] : 0u, a2 = m2 ? blist[n + 512u] : 0u,
                                    a3 = m3 ? blist[n + 768u] : 0u;
-                    q0 = *reinterpret_cast<const uint4 *>(gl + a0);
-                    q1 = *reinterpret_cast<const uint4 *>(gl + a1);
-                    q2 = *reinterpret_cast<const uint4 *>(gl + a2);
-                    q3 = *reinterpret_cast<const uint4 *>(gl + a3);
+                    q0 = *reinterpret_cast<const uint4 *>(gl + BK_CHUNK_OFF(a0));
+                    q1 = *reinterpret_cast<const uint4 *>(gl + BK_CHUNK_OFF(a1));
+                    q2 = *reinterpret_cast<const uint4 *>(gl + BK_CHUNK_OFF(a2));
+                    q3 = *reinterpret_cast<const uint4 *>(gl + BK_CHUNK_OFF(a3));
                     uint8_t *md = mine + (size_t)c0 * 16u;
-                    if (m0) *reinterpret_cast<uint4 *>(md) = q0;
-                    if (m1) *reinterpret_cast<uint4 *>(md + 4096) = q1;
-                    if (m2) *reinterpret_cast<uint4 *>(md + 8192) = q2;
-                    if (m3) *reinterpret_cast<uint4 *>(md + 12288) = q3;
+                    if (m0) *reinterpret_cast<uint4 *>(md) = BK_RGBA_VAL(q0, a0);
+                    if (m1) *reinterpret_cast<uint4 *>(md + 4096) = BK_RGBA_VAL(q1, a1);
+                    if (m2) *reinterpret_cast<uint4 *>(md + 8192) = BK_RGBA_VAL(q2, a2);
+                    if (m3) *reinterpret_cast<uint4 *>(md + 12288) = BK_RGBA_VAL(q3, a3);
                 }
             }
             BK_RGBA_BARRIER();                // the plane's chunks are in `buf`
-            if (c < 3) BK_RGBA_LOADS(f, c + 1);
-            else if (f + 1 < f_end) BK_RGBA_LOADS(f + 1, 0);
+            const bool more = c < 3 || f + 1 < f_end;       // another plane follows this one
+            if (c < 3) { BK_RGBA_LUT_REQUEST(c + 1); BK_RGBA_LOADS(f, c + 1); }
+            else if (more) { BK_RGBA_LUT_REQUEST(0); BK_RGBA_LOADS(f + 1, 0); }
             if (!tile_empty) {
 #pragma unroll
                 for (int r = 0; r < RG; ++r) {
@@ -115,9 +184,13 @@ __device__ __forceinline__ void rgba_frames(const uint8_t *__restrict__ globe, s
                     }
                 }
             }
+            if (more) BK_RGBA_LUT_COMMIT();   // (every wave has passed the barrier above: nobody reads this plane's LUT any more)
             BK_RGBA_BARRIER();                // every wave is done with `buf`
         }
     }
+#undef BK_RGBA_VAL
+#undef BK_RGBA_LUT_COMMIT
+#undef BK_RGBA_LUT_REQUEST
 #undef BK_RGBA_BARRIER
 #undef BK_RGBA_LOADS
 #undef BK_RGBA_PLANE
@@ -141,10 +214,12 @@ __device__ __forceinline__ CoopIdx<RG> rgba_load_idx(const uint16_t *__restrict_
 }
 
 // truecolour frames of a block the staging does not serve: straight from the lensmap, pixel by pixel
-template <int RG>
+// RUBIX: the pixel's tint from the lensmap's tint plane ([rows][W], as coop_slow_frames), its four bytes through the LUTs in device memory
+template <int RG, bool RUBIX>
 __device__ __forceinline__ void rgba_direct_frames(const uint32_t *__restrict__ lmap, const uint8_t *__restrict__ globe, size_t globe_stride,
                                                    int tglobes, int globe0, int f_begin, int f_end, uint8_t *__restrict__ dst, int dst_pitch,
-                                                   size_t frame_stride, int W, int rows, int row0, int x)
+                                                   size_t frame_stride, int W, int rows, int row0, int x,
+                                                   const uint8_t *__restrict__ tints, const uint8_t *__restrict__ lut)
 {
     if (row0 >= rows) return;
     for (int f = f_begin; f < f_end; ++f) {
@@ -154,21 +229,31 @@ __device__ __forceinline__ void rgba_direct_frames(const uint32_t *__restrict__ 
             if (x + i >= W) break;
             const uint32_t o = lmap[(size_t)row0 * W + x + i];
             if (o == BK_NULL_OFFSET) continue;
-            out[i] = (uint32_t)p0[o] | ((uint32_t)p0[globe_stride + o] << 8) | ((uint32_t)p0[2 * globe_stride + o] << 16) |
-                     ((uint32_t)p0[3 * globe_stride + o] << 24);
+            uint32_t b0 = p0[o], b1 = p0[globe_stride + o], b2 = p0[2 * globe_stride + o], b3 = p0[3 * globe_stride + o];
+            if (RUBIX) {
+                const uint32_t t = tints[(size_t)row0 * W + x + i];
+                if (t < (uint32_t)BK_MAX_PLATES) {
+                    const uint8_t *row = lut + t * 256u;
+                    b0 = row[b0]; b1 = row[BK_PAL_BYTES + b1]; b2 = row[2 * BK_PAL_BYTES + b2]; b3 = row[3 * BK_PAL_BYTES + b3];
+                }
+            }
+            out[i] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
         }
     }
 }
 
 // globe_frames = TRUECOLOUR globes resident (ring slots / 4), frame0 = the first one, nframes / fchunk in truecolour frames; dst =
-// pixel (0, first owned row), 4 bytes per pixel.  tint_t, pal, order, bands: unused (BK_COOP_KERNEL_ARGS is the launchers' one list).
+// pixel (0, first owned row), 4 bytes per pixel.  order, bands: unused (BK_COOP_KERNEL_ARGS is the launchers' one list); tint_t and pal
+// are read by the RUBIX instantiations only - there pal = the four planes' LUTs, uint8 [4][BK_MAX_PLATES][256], and the block map is
+// the TINTED one.
 // (no amdgpu_waves_per_eu: the twelve more accumulator dwords than the 8-bit one-block form put RG = 4 at 77 VGPRs = 6 waves per SIMD;
 //  asking for 8 would spill them, and at RG = 4 the staging buffer - 18 KiB and more on real lenses - allows 8 workgroups per CU at best)
-template <int RG>
-__global__ __launch_bounds__(256) void apply_coop_rgba_kernel(BK_COOP_KERNEL_ARGS)
+template <int RG, bool RUBIX>
+__device__ __forceinline__ void rgba_workgroup(BK_COOP_KERNEL_ARGS)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     (void)tint_t; (void)pal; (void)order; (void)bands;
+    uint8_t *pal_s = smem + lds_buf;                  // RUBIX: one plane's LUT behind the staging buffer (the launch asks for BK_PAL_BYTES more)
     constexpr int N = 1024 * RG;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int blk;
@@ -186,7 +271,7 @@ __global__ __launch_bounds__(256) void apply_coop_rgba_kernel(BK_COOP_KERNEL_ARG
     const bool aligned = ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dst_pitch | (uintptr_t)frame_stride) & (uintptr_t)15) == 0;
     constexpr int LPR = 32 / RG;                      // a lane's row as in coop_compile_kernel; its pixels of that row: see the head comment
     const int ry = wave * 2 * RG + lane / LPR, cx = lane % LPR;
-    const CoopPrefetch<RG> cur = coop_fetch<false, RG>(hdr, list, blk);
+    const CoopPrefetch<RG> cur = coop_fetch<RUBIX, RG>(hdr, list, blk);
     const uint32_t nchunks = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.h.x);
     const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.h.y);
     if (flags & CF_EMPTY) return;
@@ -197,7 +282,8 @@ __global__ __launch_bounds__(256) void apply_coop_rgba_kernel(BK_COOP_KERNEL_ARG
     const bool tile_all = (flags >> wave) & 1u, tile_empty = (flags >> (4 + wave)) & 1u;
     if ((flags & CF_SLOW) || (int)(nchunks * 16u) > lds_buf) {
         if (!tile_empty)
-            rgba_direct_frames<RG>(lmap, globe, globe_stride, globe_frames, frame0, f_begin, f_end, dst, dst_pitch, frame_stride, W, rows, row0, x);
+            rgba_direct_frames<RG, RUBIX>(lmap, globe, globe_stride, globe_frames, frame0, f_begin, f_end, dst, dst_pitch, frame_stride, W, rows,
+                                          row0, x, tint_t, pal);
         return;
     }
     const CoopIdx<RG> ix = rgba_load_idx<RG>(idx, blk, wave, lane);
@@ -206,23 +292,43 @@ __global__ __launch_bounds__(256) void apply_coop_rgba_kernel(BK_COOP_KERNEL_ARG
     const uint32_t *bl = list + (size_t)blk * N;
     const bool fast_store = tile_all && aligned;
     const uint32_t nq = (nchunks + 255u) >> 8;
-#define BK_RGBA(NQ_) rgba_frames<NQ_, RG>(globe, globe_stride, globe_frames, frame0, f_begin, f_end, dst, dst_pitch, frame_stride, smem, bl, nchunks, \
-                                          s0, s1, s2, s3, k0, k1, k2, k3, ix, fast_store, tile_empty, row0, bx * 128, cx)
+#define BK_RGBA(NQ_) rgba_frames<NQ_, RG, RUBIX>(globe, globe_stride, globe_frames, frame0, f_begin, f_end, dst, dst_pitch, frame_stride, smem, bl, nchunks, \
+                                                 s0, s1, s2, s3, k0, k1, k2, k3, ix, fast_store, tile_empty, row0, bx * 128, cx, pal, pal_s)
     if (nq <= 1) BK_RGBA(1);
     else if (nq == 2) BK_RGBA(2);
     else if (nq == 3) BK_RGBA(3);
     else BK_RGBA(4);
 #undef BK_RGBA
 }
+#define BK_COOP_KERNEL_ARG_NAMES                                                                                                    \
+    hdr, list, idx, tint_t, lmap, globe, globe_stride, globe_frames, frame0, dst, dst_pitch, frame_stride, W, rows, blocks_x, nblocks, \
+    nframes, fchunk, lds_buf, pal, kflags, order, bands, wgmap
+template <int RG>
+__global__ __launch_bounds__(256) void apply_coop_rgba_kernel(BK_COOP_KERNEL_ARGS)
+{
+    rgba_workgroup<RG, false>(BK_COOP_KERNEL_ARG_NAMES);
+}
+// the tinted launch's kernel (no amdgpu_waves_per_eu either: asked for the plain kernel's 6 waves per SIMD, RG = 4 spills 60 bytes per lane)
+template <int RG>
+__global__ __launch_bounds__(256) void apply_coop_rgba_tinted_kernel(BK_COOP_KERNEL_ARGS)
+{
+    rgba_workgroup<RG, true>(BK_COOP_KERNEL_ARG_NAMES);
+}
+#undef BK_COOP_KERNEL_ARG_NAMES
 
-// dst = address of pixel (0, row0) of truecolour frame 0, i.e. the first owned row; globe0 / nframes in truecolour globes / frames
-int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst, int dst_pitch, size_t frame_stride)
+// dst = address of pixel (0, row0) of truecolour frame 0, i.e. the first owned row; globe0 / nframes in truecolour globes / frames;
+// d_lut != nullptr: the tinted launch (bk_apply_rgba_tinted_device)
+int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst, int dst_pitch, size_t frame_stride, const uint8_t *d_lut)
 {
     const int rows = ctx->rows();
     if (rows <= 0 || nframes <= 0) return BK_OK;
     const int planes = 4 * nframes;
-    if (int r = ensure_coopmap(ctx, planes, 0)) return r;        // the plain block map, compiled and tuned as for a launch of that many 8-bit frames
+    const bool rubix = d_lut != nullptr;
+    // the plain / the tinted block map, compiled and tuned as for a launch of that many 8-bit frames of that flavour (the tuning launches
+    // of a tinted map are 8-bit rubix launches through whatever ctx->d_pal holds: their output is scratch)
+    if (int r = ensure_coopmap(ctx, planes, rubix ? 1 : 0)) return r;
     CoopMap *cm = ctx->coopmap;
+    if (rubix != cm->tinted) return ctx->fail(BK_E_STATE, "truecolour apply: the block map is not of this launch's flavour (internal)");
     const int blocks_x = cm->blocks_x, nblocks = blocks_x * cm->blocks_y;
     // planes per block visit as an 8-bit launch of that many frames has them; a visit serves whole truecolour frames
     const int fchunk = std::max(1, coop_frames_per_visit(ctx, cm, planes) / 4);
@@ -235,11 +341,20 @@ int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst, int ds
     int kflags = ctx->apply_flags & 16;
     if (coop_wants_wgmap(cm, ctx->apply_flags)) kflags |= BK_KF_WGMAP;
     const dim3 grid((unsigned)(per * 8), (unsigned)fblocks);
-#define BK_APPLY_RGBA(N) hipLaunchKernelGGL((apply_coop_rgba_kernel<N>), grid, dim3(256), (size_t)lds_buf, ctx->stream, cm->d_hdr, cm->d_list, cm->d_idx, \
+#define BK_APPLY_RGBA(N, RBX) if (RBX && lds_buf + BK_PAL_BYTES > 65536)                                                                                 \
+                                  BK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(BK_RGBA_KERNEL_##RBX<N>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                                                  lds_buf + BK_PAL_BYTES));                                                                \
+                              hipLaunchKernelGGL((BK_RGBA_KERNEL_##RBX<N>), grid, dim3(256), (size_t)lds_buf + (RBX ? BK_PAL_BYTES : 0), ctx->stream, \
+                                            cm->d_hdr, cm->d_list, cm->d_idx,                                                                  \
                                             ctx->d_tints, ctx->d_offsets, ctx->d_globe, ctx->globe_stride(), ctx->nframes / 4, globe0, dst,       \
                                             dst_pitch, frame_stride, ctx->W, rows, blocks_x, nblocks, nframes, fchunk, lds_buf,               \
-                                            ctx->d_pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap)
-    if (cm->rg == 1) BK_APPLY_RGBA(1); else if (cm->rg == 2) BK_APPLY_RGBA(2); else BK_APPLY_RGBA(4);
+                                            RBX ? d_lut : ctx->d_pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap)
+#define BK_RGBA_KERNEL_true apply_coop_rgba_tinted_kernel
+#define BK_RGBA_KERNEL_false apply_coop_rgba_kernel
+    if (rubix) { if (cm->rg == 1) { BK_APPLY_RGBA(1, true); } else if (cm->rg == 2) { BK_APPLY_RGBA(2, true); } else { BK_APPLY_RGBA(4, true); } }
+    else { if (cm->rg == 1) { BK_APPLY_RGBA(1, false); } else if (cm->rg == 2) { BK_APPLY_RGBA(2, false); } else { BK_APPLY_RGBA(4, false); } }
+#undef BK_RGBA_KERNEL_true
+#undef BK_RGBA_KERNEL_false
 #undef BK_APPLY_RGBA
     BK_HIP(ctx, hipGetLastError());
     return BK_OK;

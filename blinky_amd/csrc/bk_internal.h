@@ -88,6 +88,7 @@ struct bk_ctx {
     uint8_t *d_tints = nullptr;      // [row1-row0][W]
     uint8_t *d_frame = nullptr;      // [row1-row0][W] staging for bk_apply (host dst)
     uint8_t *d_pal = nullptr;        // [6][256]
+    uint8_t *d_lut_rgba = nullptr;   // [4][6][256] the byte LUTs of bk_apply_rgba_tinted_device; a buffer of its own (d_pal stays the 8-bit palette), allocated on first use
     uint64_t *d_mask = nullptr;      // mapped bits, 1 per pixel of the owned rows
     int *d_display = nullptr;        // [6] display flags + [1] error bits + [1] flagged-entry count + [1] first malformed result (scan key + 1) written by the build kernels
     unsigned int last_bad_key = 0;   // of the last bk_build: 1 + scan key of the first pixel whose callback returned a malformed result (0 = none)
@@ -150,6 +151,9 @@ struct bk_ctx {
     uint8_t pal_cache[BK_MAX_PLATES * 256] = {}; // what d_pal holds, uploaded on pal_stream (upload_pal)
     hipStream_t pal_stream = nullptr;
     bool pal_cached = false;
+    uint8_t lut_rgba_cache[4 * BK_MAX_PLATES * 256] = {};   // what d_lut_rgba holds, uploaded on lut_rgba_stream (upload_lut_rgba)
+    hipStream_t lut_rgba_stream = nullptr;
+    bool lut_rgba_cached = false;
     bool res_rubix = false;
     bool apply_was_resident = false;      // latched by bk_apply_begin: the frame in flight went to the resident kernel
     bk::LensProgram *prog = nullptr;      // owned; freed with bk::lensprogram_free
@@ -207,8 +211,10 @@ int launch_truncate_scan(bk_ctx *ctx, unsigned int bad_key, int display_out[BK_M
 void coopmap_invalidate(bk_ctx *ctx);
 int launch_apply_coop(bk_ctx *ctx, int frame0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch,
                       size_t frame_stride, int rubix_on);
-// bk_apply_rgba.inc (part of bk_apply_coop.hip): truecolour frames from truecolour globes (four ring slots each)
-int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch, size_t frame_stride);
+// bk_apply_rgba.inc (part of bk_apply_coop.hip): truecolour frames from truecolour globes (four ring slots each);
+// d_lut = nullptr: the plain launch, else the tinted one through the device copy of uint8 [4][BK_MAX_PLATES][256]
+int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch, size_t frame_stride,
+                      const uint8_t *d_lut = nullptr);
 int coopmap_stats(bk_ctx *ctx, int out[6]);   // blocks, direct-gather blocks, empty blocks, LDS bytes per buffer
 int coopmap_traffic_model(bk_ctx *ctx, uint64_t out[8]);
 int coopmap_xcd_probe(bk_ctx *ctx, int *out, int nwg);

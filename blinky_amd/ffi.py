@@ -76,6 +76,7 @@ _SIGS = {
     "bk_upload_plate_rgba": (_i, [_vp, _i, _i, _vp, _i]),
     "bk_upload_plate_rgba_device": (_i, [_vp, _i, _i, _vp, _i]),
     "bk_apply_rgba_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i]),
+    "bk_apply_rgba_tinted_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
     "bk_globe_device_ptr": (_vp, [_vp, _i]),
     "bk_fill_plate_lcg": (_i, [_vp, _i, _i, C.c_uint32]),
     "bk_apply": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
@@ -89,6 +90,7 @@ _SIGS = {
     "bk_apply_resident_info": (_i, [_vp, C.POINTER(_i)]),
     "bk_apply_end": (_i, [_vp, _vp, _i, _i, _i]),
     "bk_create_palmap": (None, [_vp, _vp]),
+    "bk_create_tintmap_rgba": (None, [_vp, _vp]),
     "bk_get_size": (_i, [_vp] + [C.POINTER(_i)] * 5),
     "bk_version": (C.c_char_p, []),
     "bk_set_apply_variant": (_i, [_vp, _i]),
@@ -443,6 +445,15 @@ class Context:
     def apply_rgba_device(self, dst_ptr, pitch, frame_stride, globe0=0, nframes=1, x0=0, y0=0):
         """truecolour frames (4 bytes per pixel) from truecolour globes; pitch / frame_stride in bytes, x0 / y0 in pixels"""
         self._chk(lib.bk_apply_rgba_device(self._h, globe0, nframes, dst_ptr, pitch, frame_stride, x0, y0))
+
+    def apply_rgba_tinted_device(self, dst_ptr, pitch, frame_stride, lut, globe0=0, nframes=1, x0=0, y0=0):
+        """apply_rgba_device with rubix: byte c of a mapped pixel of tint t < 6 leaves as lut[c][t][v]; lut: uint8 [4][6][256]
+        (create_tintmap_rgba makes the reference's tints)"""
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8)
+            if lut.shape != (4, MAX_PLATES, 256):
+                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        self._chk(lib.bk_apply_rgba_tinted_device(self._h, globe0, nframes, dst_ptr, pitch, frame_stride, x0, y0, _ptr(lut)))
 
     # ---- the resident single-frame apply (bk_apply_resident_*): one kernel stays on the device, frames are commands
     def resident_begin(self, rubix_on=False, pal=None, idle_ms=0.0):
@@ -839,6 +850,15 @@ def create_palmap(basepal):
     basepal = np.ascontiguousarray(basepal, dtype=np.uint8)
     out = np.empty((MAX_PLATES, 256), np.uint8)
     lib.bk_create_palmap(_ptr(basepal), _ptr(out))
+    return out
+
+
+def create_tintmap_rgba(channel_of_byte=(0, 1, 2, 3)):
+    """the reference's rubix tints as byte LUTs for Context.apply_rgba_tinted_device: uint8 [4][6][256]; channel_of_byte[c] = 0 / 1 / 2
+    for red / green / blue, anything else (alpha) = identity"""
+    ch = (_i * 4)(*[int(c) for c in channel_of_byte])
+    out = np.empty((4, MAX_PLATES, 256), np.uint8)
+    lib.bk_create_tintmap_rgba(ch, _ptr(out))
     return out
 
 

@@ -21,7 +21,7 @@
  *   - there is no CPU fallback: without a usable GPU bk_create fails.
  *   - texels and pixels are 8-bit palettised, as the reference's (TyrQuake's software rasteriser).  TRUECOLOUR - 32-bit plates
  *     warped into 32-bit frames, for hosts whose plates are frame buffers of a present-day renderer - is bk_upload_plate_rgba /
- *     bk_upload_plate_rgba_device / bk_apply_rgba_device: a 32-bit globe is four byte planes in four consecutive slots of the same
+ *     bk_upload_plate_rgba_device / bk_apply_rgba_device / bk_apply_rgba_tinted_device: a 32-bit globe is four byte planes in four consecutive slots of the same
  *     globe ring, so lens build, lensmap and everything else in this header are shared with the 8-bit path as they are.
  */
 #ifndef BLINKY_HIP_H
@@ -258,11 +258,27 @@ int bk_apply_device(bk_ctx *ctx, int frame0, int nframes, void *dst_dev, int dst
  * BK_E_INVALID: dst_pitch < 4 * (W + x0), a negative origin, globe0 or nframes < 1, or dst / dst_pitch / frame_stride not a multiple
  * of 4.  BK_E_STATE: no lensmap; fewer than 4 ring slots; bk_set_apply_variant(0) (the staged variant only, as for the resident
  * apply); a BK_DEVICE_NONE context.
- * Out of scope: rubix tints on truecolour frames; the resident kernel; a host-pointer bk_apply_rgba; the bk_comm_* / bk_multi_*
+ * Rubix tints on truecolour frames: bk_apply_rgba_tinted_device below.
+ * Out of scope: the resident kernel; a host-pointer bk_apply_rgba; the bk_comm_* / bk_multi_*
  * exchanges, whose stripe buffers are W bytes per row (stripe CONTEXTS - bk_set_rows - do work); the drop-in fisheye_hip.c, whose
  * engine is 8-bit; texel filtering (nearest texel, as everywhere). */
 int bk_apply_rgba_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch,
                          size_t frame_stride, int x0, int y0);
+/* bk_apply_rgba_tinted_device: f_rubix on truecolour frames.  The reference tints a plate's palette (create_palmap, fisheye.c:857-908:
+ * a per-channel blend, fisheye.c:895-901, then the closest palette index) and render_lensmap sends a pixel whose tint is a plate's
+ * number through that plate's palette (fisheye.c:2406-2424).  A truecolour texel has no palette to be quantised to: the blend itself is
+ * a byte -> byte table per (byte of the texel, plate), and that is what this call takes.  It is bk_apply_rgba_device in every respect -
+ * addressing, alignment, owned rows, untouched unmapped pixels, asynchronous on the context's stream, ending a resident session, the
+ * same BK_E_INVALID / BK_E_STATE cases - except that byte c of a mapped pixel whose tint t (lens.pixel_tints, fisheye.c:432-449) is
+ * below BK_MAX_PLATES is stored as lut[c][t][v] instead of v; tints of 255 and every other value >= BK_MAX_PLATES leave the texel as it
+ * is, as in the 8-bit rubix apply.  lut == NULL is BK_E_INVALID.  The tables are generic: per-plate grading or gamma are the same call;
+ * bk_create_tintmap_rgba makes the reference's.  The device copy of the 6144 bytes is kept while the bytes and the stream stay the
+ * same; it is apart from the 8-bit palette's, so 8-bit rubix launches and truecolour ones alternate without uploads.
+ * The launch runs over the TINTED block map (both flavours are kept: alternating with plain launches swaps, it does not recompile).
+ * Out of scope: the resident kernel; a host-pointer call; the bk_comm_* / bk_multi_* exchanges; the drop-in fisheye_hip.c; texel
+ * filtering; tints of different strength per pixel - beyond what a caller's own tables express. */
+int bk_apply_rgba_tinted_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch,
+                                size_t frame_stride, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256]);
 
 /* ---- resident single-frame apply ------------------------------------------------------------------------------------
  * replaces: the per-frame call of render_lensmap (fisheye.c:803 -> 2406-2424) for hosts whose globes stay in device memory.
@@ -410,6 +426,11 @@ int   bk_dev_read(bk_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes
 
 /* rubix palettes: create_palmap / find_closest_pal_index (fisheye.c:835-908); basepal = 768 bytes */
 void bk_create_palmap(const uint8_t *basepal, uint8_t pal_out[BK_MAX_PLATES][256]);
+/* the same tints for truecolour texels (bk_apply_rgba_tinted_device): create_palmap's blend (fisheye.c:895-901) of the six tint colours
+ * (fisheye.c:863-886) at percent = 256/6 (fisheye.c:860), without the palette search that follows it there (fisheye.c:903):
+ * lut_out[c][j][v] = clamp(v + ((42 * (tint[j][ch] - v)) >> 8)), ch = channel_of_byte[c]: 0 = red, 1 = green, 2 = blue; any other
+ * value (alpha, padding): the identity.  RGBA texels: {0, 1, 2, 3}; BGRA: {2, 1, 0, 3}.  Host code; no context, no device. */
+void bk_create_tintmap_rgba(const int channel_of_byte[4], uint8_t lut_out[4][BK_MAX_PLATES][256]);
 
 /* ---- introspection ---------------------------------------------------------------------
  * (developer knobs, ablations, statistics and test hooks - the bk_debug_* entry points - are declared in

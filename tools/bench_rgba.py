@@ -7,7 +7,14 @@ At 3840x2160 cube/panini and cube/hammer, over the 64-slot LCG ring of the bench
 B's output is compared with A's plane by plane before anything is timed.  Timing: HIP events on the context's stream, warm-up
 launches first, regions of at least --region seconds made of ten event-timed trains of launches (a region's figure is the median
 train), A / B / A / B ... alternated --repeats times inside this one process.  The target: B's median <= A's median + A's own spread
-(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE]"""
+(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE]
+
+--tint: the same protocol for f_rubix on truecolour frames, three launches alternated A' / B' / B:
+  A'  one bk_apply_device launch of 64 8-bit frames with rubix_on = 1 (existing code: the same bytes through the same number of LUT
+      passes per chunk)
+  B'  one bk_apply_rgba_tinted_device launch of 16 truecolour frames with lut[c] = that same palette for all four c
+  B   the plain truecolour launch
+B' must equal A' plane by plane before anything is timed.  The target: B''s median <= A''s median + A''s own spread."""
 import argparse
 import json
 import os
@@ -18,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import blinky_amd  # noqa: E402
@@ -91,15 +99,95 @@ def measure(lens, repeats, region_s):
                 compulsory_bytes_per_truecolour_frame=bytes_min, compulsory_tb_s=bytes_min * (SLOTS // 4) / med_b / 1e12, target_met=bool(med_b <= med_a + spread))
 
 
+def measure_tint(lens, repeats, region_s):
+    ctx = blinky_amd.Context(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_frames(SLOTS)
+    S.configure(ctx, "cube", lens, None, (W, H))
+    ctx.build()
+    for f in range(SLOTS):
+        for p in range(6):
+            ctx.fill_plate_lcg(f, p, seed_frame=f)
+    pal = blinky_amd.ffi.create_palmap(((np.arange(768) * 37) % 256).astype(np.uint8))
+    lut = np.ascontiguousarray(np.broadcast_to(pal, (4, 6, 256)))
+    out_a = torch.zeros((SLOTS, H, W), dtype=torch.uint8, device="cuda")
+    out_t = torch.zeros((SLOTS // 4, H, W, 4), dtype=torch.uint8, device="cuda")
+    out_b = torch.zeros((SLOTS // 4, H, W, 4), dtype=torch.uint8, device="cuda")
+
+    def a():
+        ctx.apply_device(out_a.data_ptr(), W, H * W, frame0=0, nframes=SLOTS, rubix_on=True, pal=pal)
+
+    def t():
+        ctx.apply_rgba_tinted_device(out_t.data_ptr(), 4 * W, 4 * W * H, lut, globe0=0, nframes=SLOTS // 4)
+
+    def b():
+        ctx.apply_rgba_device(out_b.data_ptr(), 4 * W, 4 * W * H, globe0=0, nframes=SLOTS // 4)
+
+    for _ in range(3):                                     # warm-up: the first launches compile and tune the block map of either flavour
+        a()
+        t()
+        b()
+    torch.cuda.synchronize()
+    planar = out_t.permute(0, 3, 1, 2).reshape(SLOTS, H, W)
+    if not torch.equal(planar, out_a):
+        bad = int((planar != out_a).sum())
+        raise SystemExit(f"{lens}: the tinted truecolour frames differ from the 8-bit rubix frames of the same slots in {bad} bytes - nothing timed")
+    tinted_bytes = int((out_t != out_b).sum())
+    del planar
+    a()                                                    # the statistics below: of the TINTED block map
+    torch.cuda.synchronize()
+    st = ctx.tile_stats()
+    pilot = min(region(stream, a, 4, trains=3), region(stream, t, 4, trains=3), region(stream, b, 4, trains=3))
+    per_train = max(2, int(region_s / 10 / pilot) + 1)
+    ra, rt, rb = [], [], []
+    for _ in range(repeats):
+        ra.append(region(stream, a, per_train))
+        rt.append(region(stream, t, per_train))
+        rb.append(region(stream, b, per_train))
+    ctx.close()
+    med_a, med_t, med_b, spread = statistics.median(ra), statistics.median(rt), statistics.median(rb), max(ra) - min(ra)
+    return dict(lens=lens, W=W, H=H, tinted_block=f"128x{st['tile_h'] % 1000}", tinted_lds_kib=st["lds_bytes_per_wave"] // 1024,
+                tinted_slow_blocks=st["slow"], launches_per_train=per_train, bytes_changed_by_the_tint=tinted_bytes,
+                a_regions_us=[x * 1e6 for x in ra], t_regions_us=[x * 1e6 for x in rt], b_regions_us=[x * 1e6 for x in rb],
+                a_us=med_a * 1e6, t_us=med_t * 1e6, b_us=med_b * 1e6, a_spread_us=spread * 1e6, t_over_a=med_t / med_a, t_over_b=med_t / med_b,
+                target_met=bool(med_t <= med_a + spread))
+
+
+def fmt(ts):
+    return ", ".join("%.1f" % x for x in ts)
+
+
+def main_tint(args):
+    rows = []
+    for lens in args.lenses.split(","):
+        r = measure_tint(lens, args.repeats, max(0.2, args.region))
+        rows.append(r)
+        print(f"4K cube/{lens}, f_rubix [tinted block map: {r['tinted_block']} blocks, {r['tinted_lds_kib']} KiB staging + 1.5 KiB LUT, "
+              f"{r['tinted_slow_blocks']} blocks without staging], {r['launches_per_train']} launches per train, {args.repeats} x A'/B'/B alternated:\n"
+              f"  A' 64 8-bit frames, rubix      {r['a_us']:8.1f} us per launch (regions {fmt(r['a_regions_us'])}; spread {r['a_spread_us']:.1f})\n"
+              f"  B' 16 truecolour frames, tinted {r['t_us']:7.1f} us per launch (regions {fmt(r['t_regions_us'])})\n"
+              f"  B  16 truecolour frames, plain  {r['b_us']:7.1f} us per launch (regions {fmt(r['b_regions_us'])})\n"
+              f"  B' == A' plane by plane ({r['bytes_changed_by_the_tint']} bytes differ from the plain frames); B' / A' = {r['t_over_a']:.3f}; "
+              f"B' / B = {r['t_over_b']:.3f}; target B' <= A' + spread: {'met' if r['target_met'] else 'MISSED'}", flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lenses", default="panini,hammer")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--region", type=float, default=0.25, help="seconds per timed region (at least 0.2)")
     ap.add_argument("--out", default=None, help="also write the results as JSON lines to this file")
+    ap.add_argument("--tint", action="store_true", help="f_rubix: 8-bit rubix launch A' / tinted truecolour B' / plain truecolour B")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_rgba.py measures on the GPU; there is none here")
+    if args.tint:
+        return main_tint(args)
     rows = []
     for lens in args.lenses.split(","):
         r = measure(lens, args.repeats, max(0.2, args.region))
