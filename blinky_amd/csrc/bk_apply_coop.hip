@@ -48,8 +48,59 @@ constexpr uint32_t CF_ALL = 0x1, CF_NONE = 0x10;       // << wave: that wave's r
 constexpr uint32_t CF_SLOW = 0x100, CF_EMPTY = 0x200;  // direct-gather block / nothing mapped in the block
 constexpr uint32_t BK_COOP_BINS = 65;                  // LDS-need histogram: 1 KiB bins, 0..64 KiB
 constexpr int BK_COOP_STATS = 208;                     // words per stats replica
-constexpr int BK_KF_WGMAP = 1 << 30;                   // kflags (set by the launcher): one-block form reads CoopMap::d_wgmap
 constexpr int BK_COOP_BLOCK_COST = 4;                  // what a block costs beyond its lines and pixels, in lines (barriers, header)
+
+// The `kflags` word of the apply kernels, and the developer word it starts from (bk_ctx::apply_flags, bk_debug_set_ablation).  The values
+// are ABI: tests and tools pass raw numbers.  Three kinds of kernel read the word, each its own set of bits:
+//   the batch kernels (apply_coop_kernel, apply_coop_once_kernel) get ALL of apply_flags, read as BkAblation, plus BK_KF_WGMAP;
+//   the truecolour kernels (bk_apply_rgba.inc) get BK_AB_ROW_MAJOR and BK_KF_WGMAP, nothing else;
+//   the resident kernel (bk_apply_resident.inc) gets apply_flags & BK_RF_KERNEL_MASK, read as BkResidentFlag, plus BK_KF_DIRECT, and ORs
+//   the two BK_KF_ALIGNED bits in per command for coop_gather_store<.., WT = true> - the rest of BkResidentFlag steers res_launch only.
+// Several VALUES mean different things in different sets (2048: BK_AB_SYNCTHREADS, BK_RF_NO_ONE_BLOCK, BK_KF_ALIGNED16; 16 and 4096
+// likewise).  What keeps them apart is BK_RF_KERNEL_MASK: no batch-only bit and no launcher-only bit ever reaches the resident kernel,
+// so the only 2048 it can see is the alignment bit it set itself (asserted below).
+enum BkAblation : int {                // apply_flags as the batch launch and its kernels read it
+    BK_AB_NO_GLOBE_LOADS = 2,          // (results are wrong while this or the next is set)
+    BK_AB_NO_STORES = 4,
+    BK_AB_NO_PIPELINE = 8,             // frame f + 1's loads are not issued before frame f's gather
+    BK_AB_ROW_MAJOR = 16,              // row-major block walk (bk_block_at)
+    BK_AB_PERSISTENT = 32,             // persistent form always
+    BK_AB_EQUAL_COUNT_BANDS = 64,      // XCD bands of equal block count instead of equal cost
+    BK_AB_NT_GLOBE = 128,              // non-temporal globe loads
+    BK_AB_LDS_DMA = 256,               // LDS-DMA staging in single-frame launches of the one-block form
+    BK_AB_NO_AUTO_NT_DMA = 512,        // no automatic choice of 128 / 256 for single-frame launches
+    BK_AB_SYNCTHREADS = 2048,          // __syncthreads() instead of the raw LDS barrier (BK_LDS_BARRIER)
+    BK_AB_NO_WIDE_PLAN = 4096,         // never the six-chunks-per-thread register plan of the strided walk
+    BK_AB_NO_TINT = 65536,             // rubix timing without the tint (BK_CHUNK_VAL)
+};
+enum BkResidentFlag : int {            // the same word as the resident launcher (res_launch) and its kernel read it
+    BK_RF_NO_STORES = 4,
+    BK_RF_SINGLE_FRAMES = 8,           // every frame on its own
+    BK_RF_NO_STRIDE = 16,              // no frame stride
+    BK_RF_NO_ONE_BLOCK = 2048,         // not the one-block form
+    BK_RF_NO_TABLES = 4096,            // no table forms
+    BK_RF_WG_TIMING = 8192,            // time every workgroup's frames
+};
+constexpr int BK_RF_KERNEL_MASK = BK_RF_NO_STORES | BK_RF_SINGLE_FRAMES | BK_RF_WG_TIMING;     // what res_launch passes on to its kernel
+// set by the launchers / the resident kernel, never by the developer word
+constexpr int BK_KF_ALIGNED4 = 1024;                   // resident kernel, per command: the frame is 4-byte aligned ...
+constexpr int BK_KF_ALIGNED16 = 2048;                  // ... 16-byte aligned (coop_gather_store<.., WT = true>)
+constexpr int BK_KF_DIRECT = 1 << 27;                  // resident kernel: commands arrive in the device copies straight from the host (PCIe BAR)
+constexpr int BK_KF_WGMAP = 1 << 30;                   // one-block form reads CoopMap::d_wgmap
+static_assert((BK_RF_KERNEL_MASK & (BK_KF_ALIGNED4 | BK_KF_ALIGNED16)) == 0, "a developer bit would read as a frame alignment in the resident kernel");
+static_assert((int)BK_RF_NO_STORES == (int)BK_AB_NO_STORES, "coop_gather_store reads one no-stores bit for the batch and the resident kernel");
+
+// words of a statistics replica (CoopMap::d_stats, CoopMap::stats)
+constexpr int CS_MAX_CHUNKS = 0;                       // most chunks of a listed block
+constexpr int CS_SLOW_BLOCKS = 1;                      // direct-gather blocks
+constexpr int CS_EMPTY_BLOCKS = 2;
+constexpr int CS_LINES = 3;                            // 128-byte lines staged
+constexpr int CS_CHUNKS = 4;                           // chunks staged
+constexpr int CS_UNEVEN_BANDS = 7;                     // (replica 0, coop_order_kernel) XCD bands of equal block count would be more than 10 % uneven
+constexpr int CS_HIST_BLOCKS = 8;                      // [BK_COOP_BINS] blocks by LDS need (1 KiB bins) ...
+constexpr int CS_HIST_LINES = CS_HIST_BLOCKS + BK_COOP_BINS;       // ... the 128-byte lines of those blocks ...
+constexpr int CS_HIST_CHUNKS = CS_HIST_LINES + BK_COOP_BINS;       // ... and their chunks
+static_assert(CS_HIST_CHUNKS + (int)BK_COOP_BINS <= BK_COOP_STATS, "a statistics replica holds the three histograms");
 
 struct CoopHdr {              // 8 bytes per block
     uint32_t nchunks;         // entries of the block's chunk list (0 for direct-gather / empty blocks)
@@ -79,10 +130,8 @@ struct CoopMap {
     uint32_t *d_cum = nullptr;      // [nblocks] inclusive cost prefix over d_order (scratch of coop_order_kernel)
     uint32_t *d_bands = nullptr;    // [9] start of band k in d_order; [8] = live blocks
     uint32_t *d_wgmap = nullptr;    // [8 * ceil(nblocks / 8)] one-block-per-workgroup form: the block of workgroup b (XCD b % 8 takes
-                                    // band b % 8), 0xFFFFFFFF = none; used when equal-count bands would be uneven (stats[7])
-    uint32_t *d_stats = nullptr;    // 64 replicas of: [0] max chunks, [1] direct-gather blocks, [2] empty blocks,
-                                    // [3] 128-B lines staged, [4] chunks staged, [8..73) blocks by LDS need (1 KiB bins),
-                                    // [73..138) 128-B lines of those blocks, [138..203) chunks of those blocks
+                                    // band b % 8), 0xFFFFFFFF = none; used when equal-count bands would be uneven (CS_UNEVEN_BANDS)
+    uint32_t *d_stats = nullptr;    // 64 replicas of BK_COOP_STATS words, indexed by the CS_ names above
     int blocks_x = 0, blocks_y = 0;
     int rg = 4;
     int lds_bytes = 0;              // bytes of the staging buffer of the apply launch
@@ -255,16 +304,16 @@ __global__ __launch_bounds__(256) void coop_compile_kernel(const uint32_t *__res
         }
         uint32_t *st = stats + (blk & 63) * BK_COOP_STATS;
         if (!slow && any_blk) {
-            atomicMax(&st[0], nchunks);
+            atomicMax(&st[CS_MAX_CHUNKS], nchunks);
             const uint32_t bin = min(BK_COOP_BINS - 1u, (nchunks * 16u + 1023u) / 1024u);
-            atomicAdd(&st[8 + bin], 1u);
-            atomicAdd(&st[8 + BK_COOP_BINS + bin], lines);
-            atomicAdd(&st[8 + 2 * BK_COOP_BINS + bin], nchunks);
-            atomicAdd(&st[3], lines);
-            atomicAdd(&st[4], nchunks);
+            atomicAdd(&st[CS_HIST_BLOCKS + bin], 1u);
+            atomicAdd(&st[CS_HIST_LINES + bin], lines);
+            atomicAdd(&st[CS_HIST_CHUNKS + bin], nchunks);
+            atomicAdd(&st[CS_LINES], lines);
+            atomicAdd(&st[CS_CHUNKS], nchunks);
         }
-        if (slow) atomicAdd(&st[1], 1u);
-        if (!any_blk) atomicAdd(&st[2], 1u);
+        if (slow) atomicAdd(&st[CS_SLOW_BLOCKS], 1u);
+        if (!any_blk) atomicAdd(&st[CS_EMPTY_BLOCKS], 1u);
     }
 }
 
@@ -274,10 +323,10 @@ __global__ __launch_bounds__(256) void coop_compile_kernel(const uint32_t *__res
 // The staging buffer's two barriers order LDS traffic only - chunks written / gather done.  __syncthreads() is a workgroup-scope FENCE as
 // well: hipcc puts an s_waitcnt vmcnt(0) at it, which makes every wave wait there for the frame stores it has just issued and for the
 // next frame's globe loads it has just put in flight - the very latency the pipelining is meant to hide.  No wave of this kernel reads global
-// memory another wave wrote, so the raw barrier with the LDS counter alone is enough (ablation bit 2048 restores __syncthreads()).
+// memory another wave wrote, so the raw barrier with the LDS counter alone is enough (BK_AB_SYNCTHREADS, 2048, restores __syncthreads()).
 #define BK_LDS_BARRIER()                                                           \
     do {                                                                           \
-        if (kflags & 2048) __syncthreads();                                        \
+        if (kflags & BK_AB_SYNCTHREADS) __syncthreads();                           \
         else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       \
     } while (0)
 
@@ -302,7 +351,7 @@ __device__ __forceinline__ uint4 bk_tint_chunk(uint4 q, uint32_t e, const uint8_
     return q;
 }
 #define BK_CHUNK_OFF(E_) (RUBIX ? (E_) & ~15u : (E_))            /* a list entry's byte offset into the globe frame */
-#define BK_CHUNK_VAL(Q_, E_) (RUBIX && !(kflags & 65536) ? bk_tint_chunk((Q_), (E_), pal_s) : (Q_))   /* (developer bit 65536: timing without the tint) */
+#define BK_CHUNK_VAL(Q_, E_) (RUBIX && !(kflags & BK_AB_NO_TINT) ? bk_tint_chunk((Q_), (E_), pal_s) : (Q_))   /* (developer bit BK_AB_NO_TINT: timing without the tint) */
 // What a thread fetches ahead for its workgroup's NEXT block: the header (a vector load, so that it
 // is tracked by vmcnt like everything else) and its first four chunk-list entries.  The per-pixel LDS addresses are
 // loaded by coop_block itself: they are not needed before the first gather, so that load rides behind the header and
@@ -319,10 +368,10 @@ struct CoopPrefetch {
 // moment - consecutive positions - cover a compact 2-D region of the screen: the globe lines that vertically
 // neighbouring blocks share (1.3-1.4x of the distinct lines are staged, summed over blocks) are then requested close
 // together in time and meet in L2 instead of going to HBM twice (8K hammer x 64 frames: 34.6 -> 33.9 us/frame; 4K
-// hammer 9.0 -> 8.8, panini 3.83 -> 3.71; quincuncial 8.3 -> 8.5).  Ablation bit 16 restores the row-major walk.
+// hammer 9.0 -> 8.8, panini 3.83 -> 3.71; quincuncial 8.3 -> 8.5).  BK_AB_ROW_MAJOR (16) restores the row-major walk.
 __device__ __forceinline__ int bk_block_at(int l, int blocks_x, int nblocks, int kflags)
 {
-    if (kflags & 16) return l;
+    if (kflags & BK_AB_ROW_MAJOR) return l;
     constexpr int PH = 8;
     const int blocks_y = nblocks / blocks_x, per_patch = PH * blocks_x;
     const int srow = l / per_patch, rem = l - srow * per_patch;
@@ -398,7 +447,7 @@ __device__ __forceinline__ void coop_gather_store(const uint8_t *buf, const Coop
             //  offsets, and a scratch reload in front of every globe load makes the loads wait for one another)
             if (WT) asm volatile("" ::: "memory");
         }
-        if (!(kflags & 4)) {
+        if (!(kflags & BK_AB_NO_STORES)) {
             // non-temporal stores: the frame is never read back here, and keeping it out of L2 leaves the cache to the
             // globe lines neighbouring blocks share (4K panini 3.8 -> 3.3 us/frame)
             typedef uint32_t v2u __attribute__((ext_vector_type(2)));
@@ -437,7 +486,7 @@ __device__ __forceinline__ void coop_gather_store(const uint8_t *buf, const Coop
                 asm volatile("" : "+v"(w[r]));               // (one texel at a time: sixteen conditional byte reads are not to be in flight - in registers - at once)
             }
         }
-        if (kflags & 4) return;
+        if (kflags & BK_AB_NO_STORES) return;
         typedef uint32_t v2u __attribute__((ext_vector_type(2)));
         typedef uint32_t v4u __attribute__((ext_vector_type(4)));
         uint32_t off = (uint32_t)row0 * (uint32_t)dst_pitch + (uint32_t)x;
@@ -445,7 +494,7 @@ __device__ __forceinline__ void coop_gather_store(const uint8_t *buf, const Coop
         //  and paid with spills of the chunk offsets on the path that matters: the value is opaque from here on)
         asm volatile("" : "+v"(off));
         const __amdgpu_buffer_rsrc_t rd = bk_frame_rsrc(dst);
-        const bool wide_ok = (kflags & 2048) != 0, word_ok = (kflags & 1024) != 0;      // the frame's alignment (set per command)
+        const bool wide_ok = (kflags & BK_KF_ALIGNED16) != 0, word_ok = (kflags & BK_KF_ALIGNED4) != 0;      // the frame's alignment (set per command)
         if (m == (RG == 4 ? 0xFFFFu : RG == 2 ? 0xFFu : 0xFu) && wide_ok) {
             if (RG == 1) __builtin_amdgcn_raw_buffer_store_b32(w[0], rd, (int)off, 0, 16);
             else if (RG == 2) { v2u v = {w[0], w[RG - 1]}; __builtin_amdgcn_raw_buffer_store_b64(v, rd, (int)off, 0, 16); }
@@ -500,12 +549,12 @@ __device__ __forceinline__ void coop_frames(const uint8_t *__restrict__ globe, s
     // their list and chunks synchronously every frame, two dependent trips to memory that doubled those blocks' frames
     uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0, q2 = q0, q3 = q0, q4 = q0, q5 = q0;     // (scalars, not an array: they must stay in VGPRs)
     constexpr uint32_t REG_CHUNKS = NQ > 4 ? 1536u : 1024u;           // chunks the register plan covers before the extra rounds
-    const bool pipe = (kflags & 8) == 0;      // issue frame f+1's loads before frame f's gather (ablation bit 8 turns it off)
+    const bool pipe = (kflags & BK_AB_NO_PIPELINE) == 0;      // issue frame f+1's loads before frame f's gather (BK_AB_NO_PIPELINE, 8, turns it off)
     typedef uint32_t bk_v4u __attribute__((ext_vector_type(4)));
-    // kflags bit 128: the globe chunks are fetched with the non-temporal hint (streamed through L2, evicted first), so that
+    // BK_AB_NT_GLOBE (128): the globe chunks are fetched with the non-temporal hint (streamed through L2, evicted first), so that
     // what L2 keeps from one launch to the next is the block map - headers, chunk lists, pixel addresses: the same bytes every
     // launch, and with the XCD bands fixed, the same XCD's L2 - instead of globe lines nobody will ask for again
-    const bool nt_globe = (kflags & 128) != 0;
+    const bool nt_globe = (kflags & BK_AB_NT_GLOBE) != 0;
 #define BK_COOP_LD(Q, PTR)                                                                                 \
     do {                                                                                                   \
         if (nt_globe) {                                                                                    \
@@ -546,7 +595,7 @@ __device__ __forceinline__ void coop_frames(const uint8_t *__restrict__ globe, s
                 }
             }
         } else {
-        if (!pipe && !(kflags & 2)) BK_COOP_LOADS(f);
+        if (!pipe && !(kflags & BK_AB_NO_GLOBE_LOADS)) BK_COOP_LOADS(f);
         if (k0) *reinterpret_cast<uint4 *>(mine) = BK_CHUNK_VAL(q0, s0);
         if (NQ > 1 && k1) *reinterpret_cast<uint4 *>(mine + 4096) = BK_CHUNK_VAL(q1, s1);
         if (NQ > 2 && k2) *reinterpret_cast<uint4 *>(mine + 8192) = BK_CHUNK_VAL(q2, s2);
@@ -784,14 +833,14 @@ __device__ __forceinline__ void coop_block(const CoopPrefetch<RG> &cur, int l, c
     }
 
 // persistent form: a workgroup walks a strided list of blocks and prefetches the next one.  By default the list is the
-// XCD's band of the LIVE blocks in walk order, the bands cut at equal cost (CoopMap::d_order / d_bands; ablation bit 64:
+// XCD's band of the LIVE blocks in walk order, the bands cut at equal cost (CoopMap::d_order / d_bands; BK_AB_EQUAL_COUNT_BANDS, 64:
 // bands of equal block count over all blocks, empty ones included, as in rounds 1 and 2a).
 template <bool RUBIX, int RG, int MAXQ = 4>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) void apply_coop_kernel(BK_COOP_KERNEL_ARGS)
 {
     BK_COOP_PROLOGUE;
     (void)wgmap;
-    const bool balanced = (kflags & (16 | 64)) == 0;
+    const bool balanced = (kflags & (BK_AB_ROW_MAJOR | BK_AB_EQUAL_COUNT_BANDS)) == 0;
     int l_hi = l_end;
     if (balanced) {
         l = (int)bands[band] + wg_in_band;
@@ -850,7 +899,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 
 // The live blocks in walk order, the eight band starts of equal cost, the workgroup -> block map of the one-block-per-workgroup
 // grid (8 * per workgroups, per = ceil(nblocks / 8): the same bands, none longer than `per` blocks),
-// and whether bands of equal block COUNT would be more than 10 % uneven (-> stats[7] of replica 0).  One workgroup.
+// and whether bands of equal block COUNT would be more than 10 % uneven (-> CS_UNEVEN_BANDS of replica 0).  One workgroup.
 __global__ __launch_bounds__(1024) void coop_order_kernel(const uint32_t *__restrict__ cost, int nblocks, int blocks_x, int per,
                                                           uint32_t *__restrict__ order, uint32_t *__restrict__ cum,
                                                           uint32_t *__restrict__ bands, uint32_t *__restrict__ wgmap,
@@ -911,7 +960,7 @@ __global__ __launch_bounds__(1024) void coop_order_kernel(const uint32_t *__rest
         }
         uint32_t umax = 0;
         for (int k = 0; k < 8; ++k) umax = max(umax, s_ucost[k]);
-        stats[7] = (uint64_t)umax * 80u > (uint64_t)total * 11u ? 1u : 0u;
+        stats[CS_UNEVEN_BANDS] = (uint64_t)umax * 80u > (uint64_t)total * 11u ? 1u : 0u;
     }
     __syncthreads();
     for (int b = (int)threadIdx.x; b < 8 * per; b += 1024) {
@@ -923,13 +972,21 @@ __global__ __launch_bounds__(1024) void coop_order_kernel(const uint32_t *__rest
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+// the eight buffers whose size follows the lensmap (coop_reserve allocates them)
+static void coop_release_buffers(CoopMap *cm)
+{
+    for (void **p : {(void **)&cm->d_hdr, (void **)&cm->d_list, (void **)&cm->d_idx, (void **)&cm->d_cost, (void **)&cm->d_order,
+                     (void **)&cm->d_cum, (void **)&cm->d_bands, (void **)&cm->d_wgmap}) {
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    cm->alloc_px = cm->alloc_blocks = 0;
+}
+
 void coopmap_free(CoopMap *cm)
 {
     if (!cm) return;
-    (void)hipFree(cm->d_hdr);
-    (void)hipFree(cm->d_list);
-    (void)hipFree(cm->d_idx);
-    (void)hipFree(cm->d_cost); (void)hipFree(cm->d_order); (void)hipFree(cm->d_cum); (void)hipFree(cm->d_bands); (void)hipFree(cm->d_wgmap);
+    coop_release_buffers(cm);
     (void)hipFree(cm->d_stats);
     if (cm->h_stats) (void)hipHostFree(cm->h_stats);
     if (cm->stats_ready) (void)hipEventDestroy(cm->stats_ready);
@@ -952,7 +1009,8 @@ static void fold_stats(const uint32_t *rep, uint32_t *out, uint32_t scale)
 {
     for (int k = 0; k < BK_COOP_STATS; ++k) out[k] = 0;
     for (int r = 0; r < 64; ++r) {
-        out[0] = rep[r * BK_COOP_STATS] > out[0] ? rep[r * BK_COOP_STATS] : out[0];
+        static_assert(CS_MAX_CHUNKS == 0, "the one word that is a maximum, not a sum, comes first");
+        out[CS_MAX_CHUNKS] = std::max(out[CS_MAX_CHUNKS], rep[r * BK_COOP_STATS + CS_MAX_CHUNKS]);
         for (int k = 1; k < BK_COOP_STATS; ++k) out[k] += rep[r * BK_COOP_STATS + k] * scale;
     }
 }
@@ -975,29 +1033,6 @@ static int coop_compile_launch(bk_ctx *ctx, CoopMap *cm, int rg, int row_stride,
     return BK_OK;
 }
 
-static int coop_choose_buffer(const CoopMap *cm, int rg, double npixels, int num_cus, double *cost_ns);
-static int ensure_coopmap(bk_ctx *ctx, int launch_frames = 0, int want_tinted = -1);
-
-// the statistics of the last full compile, once somebody needs them (the apply launch itself does not)
-static int coop_stats_wait(bk_ctx *ctx, CoopMap *cm)
-{
-    if (!cm->stats_pending) return BK_OK;
-    BK_HIP(ctx, hipEventSynchronize(cm->stats_ready));
-    fold_stats(cm->h_stats, cm->stats, 1);
-    // the buffer size was chosen on a survey (every 2nd / 8th row of blocks); now that the exact histogram is here, let the
-    // model look again - the buffer is a launch parameter, nothing in the block map depends on it
-    if (ctx->apply_lds_kb <= 0 && !cm->lds_fixed && (int)(cm->stats[0] * 16u) > cm->lds_bytes) {
-        double c = 0;
-        const int kb = coop_choose_buffer(cm, cm->rg, (double)ctx->W * ctx->rows(), ctx->num_cus, &c);
-        if (kb * 1024 > cm->lds_bytes) cm->lds_bytes = kb * 1024;
-    }
-    uint64_t over = 0;                         // blocks that take more than one pass through the buffer
-    for (int b = cm->lds_bytes / 1024 + 1; b < (int)BK_COOP_BINS; ++b) over += cm->stats[8 + b];
-    cm->slow_blocks = (int)(cm->stats[1] + over);
-    cm->stats_pending = false;
-    return BK_OK;
-}
-
 // Cost model (ns per frame), fitted to MI355X measurements of five lenses x three block heights x five
 // buffer sizes.  Throughput side: a staged 128-byte line ~13 ps, a staged block ~0.08 ns, a pixel ~0.5 ps.
 // Latency side: a workgroup spends ~0.9 us per chunk-per-thread and frame on a block (load -> LDS -> barrier ->
@@ -1017,18 +1052,18 @@ static int coop_choose_buffer(const CoopMap *cm, int rg, double npixels, int num
     // multi-pass straggler, and in a launch of a round or two of workgroups one straggler sets the end: 1080p
     // stereographic x16 with 10 such blocks of 510 ran 2.24 us/frame, without them 1.15)
     double live_all = 0;
-    for (int b = 0; b < (int)BK_COOP_BINS; ++b) live_all += cm->stats[8 + b];
+    for (int b = 0; b < (int)BK_COOP_BINS; ++b) live_all += cm->stats[CS_HIST_BLOCKS + b];
     for (int bin = BK_COOP_LDS_CAP / 1024; bin >= 1; --bin) {
         // blocks that need more than the buffer go through it in ceil(need / buffer) passes (slower per chunk:
         // no register plan, the list is re-read every frame)
         double lines_fit = 0, blocks_fit = 0, chunks_fit = 0, over_passes = 0, max_passes = 1, live = 0;
         for (int b = 0; b < (int)BK_COOP_BINS; ++b) {
             const double passes = b <= bin ? 1.0 : (double)((b + bin - 1) / bin);
-            if (b > bin) over_passes += passes * cm->stats[8 + b];
-            if (cm->stats[8 + b]) { live += cm->stats[8 + b]; if (passes > max_passes) max_passes = passes; }
-            lines_fit += cm->stats[8 + BK_COOP_BINS + b];
-            blocks_fit += passes * cm->stats[8 + b];
-            chunks_fit += (b <= bin ? 1.0 : 1.5) * cm->stats[8 + 2 * BK_COOP_BINS + b];
+            if (b > bin) over_passes += passes * cm->stats[CS_HIST_BLOCKS + b];
+            if (cm->stats[CS_HIST_BLOCKS + b]) { live += cm->stats[CS_HIST_BLOCKS + b]; if (passes > max_passes) max_passes = passes; }
+            lines_fit += cm->stats[CS_HIST_LINES + b];
+            blocks_fit += passes * cm->stats[CS_HIST_BLOCKS + b];
+            chunks_fit += (b <= bin ? 1.0 : 1.5) * cm->stats[CS_HIST_CHUNKS + b];
         }
         int wgs = (160 * 1024) / (bin * 1024 + BK_PAL_BYTES);
         if (wgs > vg) wgs = vg;
@@ -1041,86 +1076,127 @@ static int coop_choose_buffer(const CoopMap *cm, int rg, double npixels, int num
         // them sets the end of a launch that is only a few rounds of workgroups long (~1.2 us per extra pass, per round)
         const double rounds = 2.0 * live / ((double)num_cus * wgs);
         const double straggler = (max_passes - 1.0) * 1200.0 / (rounds > 1.0 ? rounds : 1.0);
-        const double c = cbrt(t_thr * t_thr * t_thr + t_lat * t_lat * t_lat) + 12.0 * rg * over_passes + 16.0 * rg * (double)cm->stats[1] + straggler;
+        const double c = cbrt(t_thr * t_thr * t_thr + t_lat * t_lat * t_lat) + 12.0 * rg * over_passes + 16.0 * rg * (double)cm->stats[CS_SLOW_BLOCKS] + straggler;
         if (best_c < 0 || c < best_c) { best_c = c; best_bin = bin; }
     }
     *cost_ns = best_c;
     return best_bin;
 }
 
+// the statistics of the last full compile, once somebody needs them (the apply launch itself does not)
+static int coop_stats_wait(bk_ctx *ctx, CoopMap *cm)
+{
+    if (!cm->stats_pending) return BK_OK;
+    BK_HIP(ctx, hipEventSynchronize(cm->stats_ready));
+    fold_stats(cm->h_stats, cm->stats, 1);
+    // the buffer size was chosen on a survey (every 2nd / 8th row of blocks); now that the exact histogram is here, let the
+    // model look again - the buffer is a launch parameter, nothing in the block map depends on it
+    if (ctx->apply_lds_kb <= 0 && !cm->lds_fixed && (int)(cm->stats[CS_MAX_CHUNKS] * 16u) > cm->lds_bytes) {
+        double c = 0;
+        const int kb = coop_choose_buffer(cm, cm->rg, (double)ctx->W * ctx->rows(), ctx->num_cus, &c);
+        if (kb * 1024 > cm->lds_bytes) cm->lds_bytes = kb * 1024;
+    }
+    uint64_t over = 0;                         // blocks that take more than one pass through the buffer
+    for (int b = cm->lds_bytes / 1024 + 1; b < (int)BK_COOP_BINS; ++b) over += cm->stats[CS_HIST_BLOCKS + b];
+    cm->slow_blocks = (int)(cm->stats[CS_SLOW_BLOCKS] + over);
+    cm->stats_pending = false;
+    return BK_OK;
+}
+
 static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, uint8_t *dst, int dst_pitch, size_t frame_stride, int rubix_on);
 
-// want_tinted: 1 / 0 = the launch that follows is a rubix / a plain one (CoopMap::tinted), -1 = whichever map there is
-static int ensure_coopmap(bk_ctx *ctx, int launch_frames, int want_tinted)
+// ---- the steps of ensure_coopmap (below), in the order it takes them ----
+
+// The measured choice holds for the KIND of launch it was measured with: single frames, batches of up to 16, long batches
+// (a 270-row stripe x 64 frames ran 40.8 us on the 128x8 blocks a 16-frame measurement had picked, 32.5 us on 128x16).  A caller
+// that changes kind gets a fresh measurement - ~1.5 ms once, against every launch after it (tuned_frames was written
+// and never read, throughput depended on which launch happened to come first after a build).
+static int coop_kind_of(int frames) { return frames <= 1 ? 0 : frames <= 16 ? 1 : 2; }
+
+// the block height somebody insists on (rg 1 / 2 / 4), 0 = none: ensure_coopmap's force_rg (a resident session growing its blocks), else
+// the developer knob (bk_debug_set_tile_shape).  A forced height is neither measured nor swapped for another kind's.
+static int coop_forced_rg(const bk_ctx *ctx, int force_rg)
+{
+    if (force_rg) return force_rg;
+    return ctx->tile_shape == 1 || ctx->tile_shape == 2 || ctx->tile_shape == 4 ? ctx->tile_shape : 0;
+}
+
+// a kind's record -> the launch parameters of the map (compiled at the record's block height) ...
+static void coop_tuned_apply(CoopMap *cm, const CoopMap::Tuned &t)
+{
+    cm->single_form = t.form; cm->fchunk = t.fchunk; cm->lds_bytes = t.kb * 1024; cm->lds_fixed = true; cm->tuned_frames = t.frames;
+}
+// ... and the map as it is compiled and parameterised now -> the record of the kind a launch of `frames` frames is
+// (filed under the CALLER's kind of launch: an 8K x 64 launch is measured with the 16 frames a scratch buffer holds, and
+//  filed under 16 it would be measured again on every launch)
+static void coop_tuned_record(CoopMap *cm, int frames)
+{
+    cm->tuned[coop_kind_of(frames)] = {cm->rg, cm->lds_bytes / 1024, cm->single_form, cm->fchunk, frames};
+    cm->tuned_frames = frames;
+}
+
+// The flavour.  want_tinted as ensure_coopmap's; returns the context's map of that flavour, *must_compile = it was switched to
+// and has to be compiled (the caller drains first: the buffers may be those of an older map of this flavour).
+static CoopMap *coop_take_flavour(bk_ctx *ctx, int want_tinted, bool *must_compile)
 {
     if (!ctx->coopmap) ctx->coopmap = new CoopMap();
     CoopMap *cm = ctx->coopmap;
-    bool flavour_switch = false;
-    if (want_tinted >= 0 && (want_tinted != 0) != cm->tinted) {
-        // The other flavour of the map (f_rubix was switched; a tinted map lists some chunks twice).  (r6) BOTH flavours are kept: the
-        // map this launch does not want is parked in ctx->coopmap_alt and comes back, compiled and tuned as it was, when f_rubix is
-        // switched again - a toggle used to cost a compile + tuning (~1.5 ms, a dropped frame for an engine that toggles per frame),
-        // now only the first launch of each flavour after a build does.  coopmap_invalidate invalidates both.
-        // (a resident session of the current flavour holds the current map: it leaves first, while nothing has changed yet - ending it
-        //  may finish pending frames, which come back here through res_launch asking for the flavour the map still has)
-        if (cm->valid) resident_quiesce(ctx);
-        std::swap(ctx->coopmap, ctx->coopmap_alt);
-        if (!ctx->coopmap) ctx->coopmap = new CoopMap();
-        cm = ctx->coopmap;
-        if (cm->tinted != (want_tinted != 0)) {                  // (a fresh slot)
-            cm->valid = false;
-            for (auto &t : cm->tuned) t = CoopMap::Tuned();
-            cm->flips = 0;
-            cm->tinted = want_tinted != 0;
-        }
-        flavour_switch = !cm->valid;                              // compiled below: drain first (the buffers may be those of an older map of this flavour)
-    }
-    // The measured choice (below) holds for the KIND of launch it was measured with: single frames, batches of up to 16, long batches
-    // (a 270-row stripe x 64 frames ran 40.8 us on the 128x8 blocks a 16-frame measurement had picked, 32.5 us on 128x16).  A caller
-    // that changes kind gets a fresh measurement - ~1.5 ms once, against every launch after it (tuned_frames was written
-    // and never read, throughput depended on which launch happened to come first after a build).
-    auto kind_of = [](int frames) { return frames <= 1 ? 0 : frames <= 16 ? 1 : 2; };
-    int recompile_rg = 0, recompile_kb = 0;               // != 0: this kind was measured before, on blocks of another height
-    bool retune = false;
-    if (cm->valid && ctx->blockmap_tuning && launch_frames > 0 && cm->tuned_frames > 0 && kind_of(launch_frames) != kind_of(cm->tuned_frames) &&
-        !(ctx->tile_shape == 1 || ctx->tile_shape == 2 || ctx->tile_shape == 4)) {
-        const CoopMap::Tuned &t = cm->tuned[kind_of(launch_frames)];
-        if (t.rg == cm->rg) {                            // same blocks: only launch parameters differ
-            cm->single_form = t.form; cm->fchunk = t.fchunk; cm->lds_bytes = t.kb * 1024; cm->lds_fixed = true; cm->tuned_frames = t.frames;
-            return BK_OK;
-        }
-        if (t.rg != 0) {
-            if (cm->flips >= BK_COOP_MAX_FLIPS) return BK_OK;
-            ++cm->flips;
-            recompile_rg = t.rg; recompile_kb = t.kb;
-        }
-        retune = true;
+    *must_compile = false;
+    if (want_tinted < 0 || (want_tinted != 0) == cm->tinted) return cm;
+    // The other flavour of the map (f_rubix was switched; a tinted map lists some chunks twice).  (r6) BOTH flavours are kept: the
+    // map this launch does not want is parked in ctx->coopmap_alt and comes back, compiled and tuned as it was, when f_rubix is
+    // switched again - a toggle used to cost a compile + tuning (~1.5 ms, a dropped frame for an engine that toggles per frame),
+    // now only the first launch of each flavour after a build does.  coopmap_invalidate invalidates both.
+    // (a resident session of the current flavour holds the current map: it leaves first, while nothing has changed yet - ending it
+    //  may finish pending frames, which come back here through res_launch asking for the flavour the map still has)
+    if (cm->valid) resident_quiesce(ctx);
+    std::swap(ctx->coopmap, ctx->coopmap_alt);
+    if (!ctx->coopmap) ctx->coopmap = new CoopMap();
+    cm = ctx->coopmap;
+    if (cm->tinted != (want_tinted != 0)) {                  // (a fresh slot)
         cm->valid = false;
+        for (auto &t : cm->tuned) t = CoopMap::Tuned();
+        cm->flips = 0;
+        cm->tinted = want_tinted != 0;
     }
-    if (cm->valid) return BK_OK;
-    // The block map is rewritten IN PLACE.  On the way here from a build nothing can be reading it (bk_build orders itself after the
-    // context's stream, and a caller with two streams synchronizes after a build: INTEGRATION.md); a change of kind in the middle of
-    // a caller's steady state can find launches of the old map in flight on another stream - found as a memory fault in bench.py's
-    // two-stream job - so that case drains the device first, and every compile is complete before this function returns: the launch
-    // that follows may be on one stream and the one after it on another.
-    bk::Range range("blockmap compile + tuning");
-    if (retune || flavour_switch) BK_HIP(ctx, hipDeviceSynchronize());
-    struct Settle {                                       // (every way out of this function below)
-        bk_ctx *c;
-        ~Settle() { (void)hipStreamSynchronize(c->stream); }
-    } settle{ctx};
-    if (cm->valid) return BK_OK;
+    *must_compile = !cm->valid;
+    return cm;
+}
+
+// What the map's records say about the kind of launch that follows.
+enum class CoopRecall {
+    Ready,          // the map serves this launch as it is (or with the launch parameters of its kind, put in place here)
+    Recompile,      // this kind was measured before, on blocks of another height: *before says which, the map is marked invalid
+    Measure,        // no map, or none measured for this kind: the whole way (a valid map is marked invalid)
+    GiveUp,         // BK_COOP_MAX_FLIPS recompiles spent on this lensmap: the map stays as it is
+};
+static CoopRecall coop_recall_kind(const bk_ctx *ctx, CoopMap *cm, int launch_frames, int forced, CoopMap::Tuned *before)
+{
+    if (!cm->valid) return CoopRecall::Measure;
+    if (!(ctx->blockmap_tuning && launch_frames > 0 && cm->tuned_frames > 0 && coop_kind_of(launch_frames) != coop_kind_of(cm->tuned_frames) && !forced))
+        return CoopRecall::Ready;
+    const CoopMap::Tuned &t = cm->tuned[coop_kind_of(launch_frames)];
+    if (t.rg == cm->rg) {                                // same blocks: only launch parameters differ
+        coop_tuned_apply(cm, t);
+        return CoopRecall::Ready;
+    }
+    if (t.rg != 0 && cm->flips >= BK_COOP_MAX_FLIPS) return CoopRecall::GiveUp;
+    cm->valid = false;
+    if (t.rg == 0) return CoopRecall::Measure;
+    ++cm->flips;
+    *before = t;
+    return CoopRecall::Recompile;
+}
+
+// The buffers: the eight that follow the lensmap's size (grown, never shrunk) and the statistics' own
+static int coop_reserve(bk_ctx *ctx, CoopMap *cm)
+{
     const int rows = ctx->rows();
-    const int forced = ctx->tile_shape == 1 || ctx->tile_shape == 2 || ctx->tile_shape == 4 ? ctx->tile_shape : 0;   // developer knob
     const size_t bx = (ctx->W + 127) / 128;
     const size_t max_blocks = bx * (size_t)((rows + 7) / 8);
     const size_t max_px = bx * 4 * 256 * (size_t)((rows + 31) / 32 * 4 + 4);
     if (max_px > cm->alloc_px || max_blocks > cm->alloc_blocks) {      // (the header count follows ceil(rows/8), the rest ceil(rows/32))
-        (void)hipFree(cm->d_hdr); (void)hipFree(cm->d_list); (void)hipFree(cm->d_idx);
-        (void)hipFree(cm->d_cost); (void)hipFree(cm->d_order); (void)hipFree(cm->d_cum); (void)hipFree(cm->d_bands); (void)hipFree(cm->d_wgmap);
-        cm->d_hdr = nullptr; cm->d_list = nullptr; cm->d_idx = nullptr;
-        cm->d_cost = nullptr; cm->d_order = nullptr; cm->d_cum = nullptr; cm->d_bands = nullptr; cm->d_wgmap = nullptr;
-        cm->alloc_px = cm->alloc_blocks = 0;
+        coop_release_buffers(cm);
         BK_HIP(ctx, hipMalloc((void **)&cm->d_hdr, max_blocks * sizeof(CoopHdr)));
         BK_HIP(ctx, hipMalloc((void **)&cm->d_list, max_px * sizeof(uint32_t)));
         BK_HIP(ctx, hipMalloc((void **)&cm->d_idx, max_px * sizeof(uint16_t)));
@@ -1137,213 +1213,263 @@ static int ensure_coopmap(bk_ctx *ctx, int launch_frames, int want_tinted)
         BK_HIP(ctx, hipHostMalloc((void **)&cm->h_stats, 4 * 64 * BK_COOP_STATS * sizeof(uint32_t), hipHostMallocDefault));
         BK_HIP(ctx, hipEventCreateWithFlags(&cm->stats_ready, hipEventDisableTiming));
     }
-    // Block height: the cheapest of 128x8 / 128x16 / 128x32 by the cost model, unless forced.  The model is fed by SURVEY
-    // passes that look at every 8th row of blocks and write nothing but statistics (three of them cost 3/8 of one full
-    // pass); only the winner is compiled in full, and the apply can be queued right behind it - its own statistics
-    // (tile stats, traffic model) are fetched asynchronously.  Round 1 compiled all three heights in full and then the
-    // winner again: 0.9 ms of wall time per lensmap at 4K, against 0.28 ms for the build itself.
+    return BK_OK;
+}
+
+// The block heights ranked.  The cheapest of 128x8 / 128x16 / 128x32 by the cost model, unless forced.  The model is fed by
+// SURVEY passes that look at every 8th row of blocks and write nothing but statistics (three of them cost 3/8 of one full
+// pass); only the winner is compiled in full, and the apply can be queued right behind it - its own statistics
+// (tile stats, traffic model) are fetched asynchronously.  Round 1 compiled all three heights in full and then the
+// winner again: 0.9 ms of wall time per lensmap at 4K, against 0.28 ms for the build itself.
+struct CoopCand { int rg, kb; double cost; };     // a block height with the staging buffer (KiB) and the cost (ns per frame) the model gives it
+// ranked[0 .. *nranked): the candidates, cheapest first.  *nranked = 0 where there was nothing to ask the model (a forced height with a
+// forced buffer): ranked[0] is then that height with kb = 0.  Leaves the last candidate's (scaled) survey statistics in cm->stats.
+static int coop_rank_heights(bk_ctx *ctx, CoopMap *cm, int forced, CoopCand ranked[3], int *nranked)
+{
+    const int rows = ctx->rows();
     int cand[3] = {4, 2, 1}, ncand = 3;
     if (forced) { cand[0] = forced; ncand = 1; }
-    int best_rg = cand[0], best_kb = 0;
-    int c_rg[3] = {0, 0, 0}, c_kb[3] = {0, 0, 0}, nc = 0;          // the candidates with the staging buffer the model gives each,
-    double c_cost[3] = {0, 0, 0};                                   // cheapest (by the model) first
-    if (ncand > 1 || ctx->apply_lds_kb <= 0) {
-        const int by_min = (rows + 31) / 32;
-        // (every 8th row of blocks at 4K and above, every 2nd from 1080p up, everything below: the largest block decides the
-        // buffer, and a sparse survey of a small map misses it - 1080p quincuncial, surveyed every 8th row: 40 of 306 blocks
-        // did not fit the buffer chosen, 5.0 instead of 2.1 us/frame)
-        const int stride = by_min >= 64 ? 8 : by_min >= 32 ? 2 : 1;
-        for (int i = 0; i < ncand; ++i)
-            if (int r = coop_compile_launch(ctx, cm, cand[i], stride, 1 + i)) return r;
-        BK_HIP(ctx, hipMemcpyAsync(cm->h_stats + 64 * BK_COOP_STATS, cm->d_stats + 64 * BK_COOP_STATS, (size_t)ncand * 64 * BK_COOP_STATS * sizeof(uint32_t),
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < ncand; ++i) {
-            const int by = (rows + 8 * cand[i] - 1) / (8 * cand[i]), sampled = (by + stride - 1) / stride;
-            // scale the sampled rows up to all rows (integer factor on the counts; the cost model is smooth in them)
-            const uint32_t scale = (uint32_t)((by + sampled - 1) / sampled);
-            fold_stats(cm->h_stats + (size_t)(1 + i) * 64 * BK_COOP_STATS, cm->stats, scale);
-            double c = 0;
-            const int kb = coop_choose_buffer(cm, cand[i], (double)ctx->W * rows, ctx->num_cus, &c);
-            if (g_debug.print_model) {                    // developer: the cost model's inputs, one line per candidate
-                fprintf(stderr, "MODEL %dx%d rg %d kb %d cost %.1f maxchunks %u slow %u empty %u bins", ctx->W, rows, cand[i], kb, c, cm->stats[0],
-                        cm->stats[1], cm->stats[2]);
-                for (int b = 0; b < (int)BK_COOP_BINS; ++b)
-                    if (cm->stats[8 + b]) fprintf(stderr, " %d:%u:%u:%u", b, cm->stats[8 + b], cm->stats[8 + BK_COOP_BINS + b], cm->stats[8 + 2 * BK_COOP_BINS + b]);
-                fprintf(stderr, "\n");
-            }
-            int at = nc++;
-            while (at > 0 && c_cost[at - 1] > c) { c_rg[at] = c_rg[at - 1]; c_kb[at] = c_kb[at - 1]; c_cost[at] = c_cost[at - 1]; --at; }
-            c_rg[at] = cand[i]; c_kb[at] = kb; c_cost[at] = c;
+    ranked[0] = {cand[0], 0, 0};
+    *nranked = 0;
+    if (!(ncand > 1 || ctx->apply_lds_kb <= 0)) return BK_OK;
+    const int by_min = (rows + 31) / 32;
+    // (every 8th row of blocks at 4K and above, every 2nd from 1080p up, everything below: the largest block decides the
+    // buffer, and a sparse survey of a small map misses it - 1080p quincuncial, surveyed every 8th row: 40 of 306 blocks
+    // did not fit the buffer chosen, 5.0 instead of 2.1 us/frame)
+    const int stride = by_min >= 64 ? 8 : by_min >= 32 ? 2 : 1;
+    for (int i = 0; i < ncand; ++i)
+        if (int r = coop_compile_launch(ctx, cm, cand[i], stride, 1 + i)) return r;
+    BK_HIP(ctx, hipMemcpyAsync(cm->h_stats + 64 * BK_COOP_STATS, cm->d_stats + 64 * BK_COOP_STATS, (size_t)ncand * 64 * BK_COOP_STATS * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < ncand; ++i) {
+        const int by = (rows + 8 * cand[i] - 1) / (8 * cand[i]), sampled = (by + stride - 1) / stride;
+        // scale the sampled rows up to all rows (integer factor on the counts; the cost model is smooth in them)
+        const uint32_t scale = (uint32_t)((by + sampled - 1) / sampled);
+        fold_stats(cm->h_stats + (size_t)(1 + i) * 64 * BK_COOP_STATS, cm->stats, scale);
+        double c = 0;
+        const int kb = coop_choose_buffer(cm, cand[i], (double)ctx->W * rows, ctx->num_cus, &c);
+        if (g_debug.print_model) {                    // developer: the cost model's inputs, one line per candidate
+            fprintf(stderr, "MODEL %dx%d rg %d kb %d cost %.1f maxchunks %u slow %u empty %u bins", ctx->W, rows, cand[i], kb, c, cm->stats[CS_MAX_CHUNKS],
+                    cm->stats[CS_SLOW_BLOCKS], cm->stats[CS_EMPTY_BLOCKS]);
+            for (int b = 0; b < (int)BK_COOP_BINS; ++b)
+                if (cm->stats[CS_HIST_BLOCKS + b])
+                    fprintf(stderr, " %d:%u:%u:%u", b, cm->stats[CS_HIST_BLOCKS + b], cm->stats[CS_HIST_LINES + b], cm->stats[CS_HIST_CHUNKS + b]);
+            fprintf(stderr, "\n");
         }
-        best_rg = c_rg[0]; best_kb = c_kb[0];
+        int at = (*nranked)++;
+        for (; at > 0 && ranked[at - 1].cost > c; --at) ranked[at] = ranked[at - 1];
+        ranked[at] = {cand[i], kb, c};
     }
-    auto clamp_kb = [&](int kb) {
-        if (ctx->apply_lds_kb > 0) kb = ctx->apply_lds_kb > BK_COOP_LDS_CAP / 1024 ? BK_COOP_LDS_CAP / 1024 : ctx->apply_lds_kb;   // developer knob
-        return kb < 1 ? 1 : kb;
-    };
-    auto compile_full = [&](int rg, int kb) -> int {
-        cm->rg = rg;
-        cm->blocks_x = (ctx->W + 127) / 128;
-        cm->blocks_y = (rows + 8 * rg - 1) / (8 * rg);
-        cm->lds_bytes = clamp_kb(kb) * 1024;
-        if (int r = coop_compile_launch(ctx, cm, rg, 1, 0)) return r;
-        const int nb = cm->blocks_x * cm->blocks_y;
-        hipLaunchKernelGGL(coop_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, cm->d_cost, nb, cm->blocks_x, (nb + 7) / 8,
-                           cm->d_order, cm->d_cum, cm->d_bands, cm->d_wgmap, cm->d_stats);
-        BK_HIP(ctx, hipGetLastError());
-        // its statistics travel back asynchronously; whoever needs them (launch configuration, traffic model) folds them in
-        BK_HIP(ctx, hipMemcpyAsync(cm->h_stats, cm->d_stats, 64 * BK_COOP_STATS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        BK_HIP(ctx, hipEventRecord(cm->stats_ready, ctx->stream));
-        cm->stats_pending = true;
-        return BK_OK;
-    };
-    // MEASURED choice (bk_set_blockmap_tuning, on by default): the cost model ranks the block heights, but its picks miss by
-    // 10-17 % where the launch is small (1080p hammer / quincuncial: 128x8 beats the 128x16 it picks; which side wins also moves
-    // with how cold the globe ring is).  So the candidates the model puts within 20 % of its best are compiled in full and the very
-    // launch the caller is about to make - same frame count, the context's own globe - is timed on each; the fastest stays.
-    // A lensmap is built once per lens / zoom change and applied every frame: ~0.7 ms more here for up to 17 % per frame.
-    int measured = 0;
+    return BK_OK;
+}
+
+static int coop_clamp_kb(const bk_ctx *ctx, int kb)
+{
+    if (ctx->apply_lds_kb > 0) kb = ctx->apply_lds_kb > BK_COOP_LDS_CAP / 1024 ? BK_COOP_LDS_CAP / 1024 : ctx->apply_lds_kb;   // developer knob
+    return kb < 1 ? 1 : kb;
+}
+
+// The full compile at block height 8 * rg with a staging buffer of kb KiB: block map, walk order and bands, statistics on their way
+static int coop_compile_full(bk_ctx *ctx, CoopMap *cm, int rg, int kb)
+{
+    cm->rg = rg;
+    cm->blocks_x = (ctx->W + 127) / 128;
+    cm->blocks_y = (ctx->rows() + 8 * rg - 1) / (8 * rg);
+    cm->lds_bytes = coop_clamp_kb(ctx, kb) * 1024;
+    if (int r = coop_compile_launch(ctx, cm, rg, 1, 0)) return r;
+    const int nb = cm->blocks_x * cm->blocks_y;
+    hipLaunchKernelGGL(coop_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, cm->d_cost, nb, cm->blocks_x, (nb + 7) / 8,
+                       cm->d_order, cm->d_cum, cm->d_bands, cm->d_wgmap, cm->d_stats);
+    BK_HIP(ctx, hipGetLastError());
+    // its statistics travel back asynchronously; whoever needs them (launch configuration, traffic model) folds them in
+    BK_HIP(ctx, hipMemcpyAsync(cm->h_stats, cm->d_stats, 64 * BK_COOP_STATS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    BK_HIP(ctx, hipEventRecord(cm->stats_ready, ctx->stream));
+    cm->stats_pending = true;
+    return BK_OK;
+}
+
+// The MEASURED choice (bk_set_blockmap_tuning, on by default): the cost model ranks the block heights, but its picks miss by
+// 10-17 % where the launch is small (1080p hammer / quincuncial: 128x8 beats the 128x16 it picks; which side wins also moves
+// with how cold the globe ring is).  So the candidates the model puts within 20 % of its best are compiled in full and the very
+// launch the caller is about to make - same frame count, the context's own globe - is timed on each; the fastest stays.
+// A lensmap is built once per lens / zoom change and applied every frame: ~0.7 ms more here for up to 17 % per frame.
+//
+// What is timed per candidate height (its variants, v[0] = the launcher's own rule with the model's buffer):
+// Single-frame launches have two more things worth measuring per height.  (a) The form: one block per workgroup (dealt out by
+// the hardware as places free up) or the strided walk (prefetch, but a static split) - the launcher's rule of thumb is right
+// for most maps and 10-20 % off for some.  (b) The staging buffer: a launch is a whole number of ROUNDS of blocks - 4050 live
+// blocks on 7 x 256 places are 2.26 rounds and take 3 (4K mercator: 16.5 us where its bytes cost 12.8) - and a buffer of 20 KiB
+// instead of the 21-26 KiB that hold every block lets 8 workgroups share a CU: 1.98 rounds, with the few larger blocks going
+// through the buffer in two passes.  The buffer is a launch parameter, so (b) costs no compile.
+// Batch launches have one: the frames a workgroup keeps a block for.  Eight amortise the block's plan best, but a SMALL map -
+// 1080p: 1020 blocks x 2 frame groups on ~1800 places - then does not fill the chip for the 20 us the launch lasts
+// (C2 x16 moved 0.545 of the peak); four frames per visit double the workgroups.
+struct CoopVariant { int form, kb, fchunk; };     // CoopMap::single_form, staging buffer KiB, CoopMap::fchunk
+static int coop_variants(const bk_ctx *ctx, const CoopMap *cm, int nf, int kb, CoopVariant v[6])
+{
+    int n = 0;
+    v[n++] = {0, kb, 0};
+    if (nf == 1 && ctx->apply_wgs_per_cu == 16) {
+        v[n++] = {1, kb, 0};
+        if (ctx->apply_lds_kb <= 0 && kb > 20 && kb <= 28) v[n++] = {1, 20, 0};
+    }
+    if (nf >= 8 && ctx->apply_fchunk <= 0) {
+        const long long live = (long long)cm->blocks_x * cm->blocks_y - (cm->stats_pending ? 0 : (long long)cm->stats[CS_EMPTY_BLOCKS]);
+        if (live * ((nf + 7) / 8) < 2ll * ctx->num_cus * 7) {
+            v[n++] = {0, kb, 4};
+            if (nf >= 16) { v[n++] = {0, kb, 2}; v[n++] = {0, kb, 16}; }     // (twice as many again / one workgroup per block for the whole batch)
+        }
+    }
+    return n;
+}
+
+// frames of a tuning launch: the caller's own count, as far as a scratch frame buffer of 256 MB goes - in whole groups of 8 frames
+static int coop_tuning_frames(const bk_ctx *ctx, int nf)
+{
+    const int fit = (int)std::max<size_t>(16, ((size_t)256 << 20) / std::max<size_t>(1, (size_t)ctx->rows() * ctx->W) / 8 * 8);
+    return std::min(nf > 16 && nf > fit ? fit : nf, 64);
+}
+
+struct CoopMeasured {
+    int win;                // the winner: ranked[win] ...
+    CoopVariant v;          // ... launched as this variant
+    int compiled;           // ranked[compiled] is what the map is compiled for when coop_measure returns
+};
+// times ranked[0 .. keep) with launches of nf frames; the map is left compiled for one of them, with the launch parameters of the last
+// variant timed
+static int coop_measure(bk_ctx *ctx, CoopMap *cm, const CoopCand *ranked, int keep, int nf, CoopMeasured *out)
+{
+    const int rows = ctx->rows();
+    uint8_t *scratch = nullptr;
+    hipEvent_t t0, t1;
+    bool pooled = true;                    // (stream-ordered allocation where the device has a memory pool, plain otherwise)
+    if (hipMallocAsync((void **)&scratch, (size_t)nf * rows * ctx->W, ctx->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        pooled = false;
+        BK_HIP(ctx, hipMalloc((void **)&scratch, (size_t)nf * rows * ctx->W));
+    }
+    BK_HIP(ctx, hipEventCreate(&t0));
+    BK_HIP(ctx, hipEventCreate(&t1));
+    int rc = BK_OK;
+    *out = {0, {0, ranked[0].kb, 0}, -1};
+    float best_ms = -1;
+    // every candidate: one warm-up launch, then a train of launches between two events - back to back, as a caller's
+    // steady state issues them; the globe frames advance through the context's ring from launch to launch, candidate
+    // after candidate, so that none of them is handed the cache state another one left behind
+    // (short launches - stripes, small frames - are timed on longer trains: at 10 us a launch the fixed costs and their
+    //  jitter are as large as the differences looked for)
+    const double work = (double)nf * rows * ctx->W;
+    // (r6: 5 / 3 instead of 2 for the large ones - a train of two 110 us launches picked 128x8 for 4K hammer x16 on one box and
+    //  128x16 on the next, 0.67 against 0.70 of the peak; the tuning runs once per lensmap and kind of launch)
+    const int train = work < 20e6 ? 12 : work < 40e6 ? 6 : work < 300e6 ? 5 : 3;
+    const int span = ctx->nframes > nf ? ctx->nframes - nf + 1 : 1;
+    int seq = 0;
+    // (the cost model's pick is measured LAST: when it wins - the usual case - it is what is compiled at the end, and the map is not
+    //  compiled a third time)
+    float ms_pick = -1;
+    CoopVariant pick_v = out->v;
+    for (int i = keep - 1; i >= 0 && rc == BK_OK; --i) {
+        rc = coop_compile_full(ctx, cm, ranked[i].rg, ranked[i].kb);
+        // (timed in the configuration the caller's steady state runs in: with the block map's statistics there - live
+        //  blocks, uneven bands - the launch may take another form than in the first microseconds after a compile)
+        if (rc == BK_OK) rc = coop_stats_wait(ctx, cm);
+        CoopVariant vs[6];
+        const int nv = coop_variants(ctx, cm, nf, cm->lds_bytes / 1024, vs);
+        for (int k = 0; k < nv && rc == BK_OK; ++k) {
+            cm->single_form = vs[k].form;
+            cm->fchunk = vs[k].fchunk;
+            cm->lds_bytes = coop_clamp_kb(ctx, vs[k].kb) * 1024;
+            rc = launch_compiled(ctx, cm, (seq++ * nf) % span, nf, scratch, ctx->W, (size_t)rows * ctx->W, cm->tinted ? 1 : 0);
+            if (rc == BK_OK && hipEventRecord(t0, ctx->stream) != hipSuccess) rc = ctx->fail(BK_E_HIP, "block map tuning: hipEventRecord failed");
+            for (int rep = 0; rep < train && rc == BK_OK; ++rep)
+                rc = launch_compiled(ctx, cm, (seq++ * nf) % span, nf, scratch, ctx->W, (size_t)rows * ctx->W, cm->tinted ? 1 : 0);
+            float ms = 0;
+            if (rc == BK_OK && (hipEventRecord(t1, ctx->stream) != hipSuccess || hipEventSynchronize(t1) != hipSuccess ||
+                                hipEventElapsedTime(&ms, t0, t1) != hipSuccess))
+                rc = ctx->fail(BK_E_HIP, "block map tuning: timing failed");
+            if (g_debug.print_model)
+                fprintf(stderr, "TUNE %dx%d x%d rg %d kb %d form %d frames per visit %d: %.2f us per launch\n", ctx->W, rows, nf, ranked[i].rg, vs[k].kb, vs[k].form, vs[k].fchunk ? vs[k].fchunk : 8, ms * 1e3 / train);
+            if (rc == BK_OK && (best_ms < 0 || ms < best_ms)) { best_ms = ms; out->win = i; out->v = vs[k]; }
+            if (rc == BK_OK && i == 0 && k == 0) { ms_pick = ms; pick_v = vs[k]; }
+        }
+        out->compiled = i;
+    }
+    // the first variant of candidate 0 is the cost model's pick: another one replaces it only when it is measurably (3 %) faster
+    if (rc == BK_OK && ms_pick >= 0 && !(best_ms < 0.97f * ms_pick)) { out->win = 0; out->v = pick_v; }
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
+    if (pooled) (void)hipFreeAsync(scratch, ctx->stream);
+    else { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(scratch); }
+    return rc;
+}
+
+// The block map the launch that follows needs, compiled and tuned.
+// launch_frames: 8-bit frames of that launch (0 = nobody is about to launch: statistics, row costs)
+// want_tinted: 1 / 0 = the launch that follows is a rubix / a plain one (CoopMap::tinted), -1 = whichever map there is
+// force_rg: 1 / 2 / 4 = blocks of 128 x 8 * force_rg, as the developer knob forces them (coop_forced_rg); 0 = the map's own choice
+static int ensure_coopmap(bk_ctx *ctx, int launch_frames = 0, int want_tinted = -1, int force_rg = 0)
+{
+    bool flavour_switch = false;
+    CoopMap *cm = coop_take_flavour(ctx, want_tinted, &flavour_switch);
+    const int forced = coop_forced_rg(ctx, force_rg);
+    const bool retune = cm->valid;                        // (a valid map that does not stay: launches of it may be in flight)
+    CoopMap::Tuned before;
+    const CoopRecall recall = coop_recall_kind(ctx, cm, launch_frames, forced, &before);
+    if (recall == CoopRecall::Ready || recall == CoopRecall::GiveUp) return BK_OK;
+    // The block map is rewritten IN PLACE.  On the way here from a build nothing can be reading it (bk_build orders itself after the
+    // context's stream, and a caller with two streams synchronizes after a build: INTEGRATION.md); a change of kind in the middle of
+    // a caller's steady state can find launches of the old map in flight on another stream - found as a memory fault in bench.py's
+    // two-stream job - so that case drains the device first, and every compile is complete before this function returns: the launch
+    // that follows may be on one stream and the one after it on another.
+    bk::Range range("blockmap compile + tuning");
+    if (retune || flavour_switch) BK_HIP(ctx, hipDeviceSynchronize());
+    struct Settle {                                       // (every way out of this function below)
+        bk_ctx *c;
+        ~Settle() { (void)hipStreamSynchronize(c->stream); }
+    } settle{ctx};
+    if (int r = coop_reserve(ctx, cm)) return r;
+    CoopCand ranked[3];
+    int nranked = 0;
+    if (int r = coop_rank_heights(ctx, cm, forced, ranked, &nranked)) return r;
     cm->single_form = 0;
     cm->fchunk = 0;
     cm->lds_fixed = false;
     cm->tuned_frames = 0;
-    if (recompile_rg) {                                   // measured before: compile what won then
-        const CoopMap::Tuned &t = cm->tuned[kind_of(launch_frames)];
-        if (int r = compile_full(recompile_rg, recompile_kb)) return r;
-        cm->single_form = t.form; cm->fchunk = t.fchunk; cm->lds_bytes = t.kb * 1024; cm->lds_fixed = true; cm->tuned_frames = t.frames;
+    if (recall == CoopRecall::Recompile) {                // measured before: compile what won then
+        if (int r = coop_compile_full(ctx, cm, before.rg, before.kb)) return r;
+        coop_tuned_apply(cm, before);
         cm->valid = true;
         return BK_OK;
     }
-    if (ctx->blockmap_tuning && !forced && nc > 0 && ctx->d_globe && !(ctx->apply_flags & (2 | 4 | 32))) {
+    int best_rg = ranked[0].rg, best_kb = ranked[0].kb;   // the cost model's pick (or the forced height)
+    bool winner_compiled = false;                         // the map as compiled right now is the one that stays
+    int file_frames = 0;                                  // != 0: the result is remembered for the kind of launch this many frames are
+    if (ctx->blockmap_tuning && !forced && nranked > 0 && ctx->d_globe && !(ctx->apply_flags & (BK_AB_NO_GLOBE_LOADS | BK_AB_NO_STORES | BK_AB_PERSISTENT))) {
         int keep = 1;
-        while (keep < nc && c_cost[keep] <= 1.2 * c_cost[0]) ++keep;
-        // (timed with the caller's own frame count, as far as a scratch frame buffer of 256 MB goes - in whole groups of 8 frames)
-        int nf = launch_frames > 0 ? launch_frames : (ctx->nframes >= 16 ? 16 : ctx->nframes >= 8 ? 8 : 1);
-        const int for_frames = nf;
-        {
-            const size_t frame_bytes = (size_t)rows * ctx->W;
-            const int fit = (int)std::max<size_t>(16, ((size_t)256 << 20) / std::max<size_t>(1, frame_bytes) / 8 * 8);
-            if (nf > 16 && nf > fit) nf = fit;
-            if (nf > 64) nf = 64;
-        }
-        // Single-frame launches have two more things worth measuring per height.  (a) The form: one block per workgroup (dealt out by
-        // the hardware as places free up) or the strided walk (prefetch, but a static split) - the launcher's rule of thumb is right
-        // for most maps and 10-20 % off for some.  (b) The staging buffer: a launch is a whole number of ROUNDS of blocks - 4050 live
-        // blocks on 7 x 256 places are 2.26 rounds and take 3 (4K mercator: 16.5 us where its bytes cost 12.8) - and a buffer of 20 KiB
-        // instead of the 21-26 KiB that hold every block lets 8 workgroups share a CU: 1.98 rounds, with the few larger blocks going
-        // through the buffer in two passes.  The buffer is a launch parameter, so (b) costs no compile.
-        // Batch launches have one: the frames a workgroup keeps a block for.  Eight amortise the block's plan best, but a SMALL map -
-        // 1080p: 1020 blocks x 2 frame groups on ~1800 places - then does not fill the chip for the 20 us the launch lasts
-        // (C2 x16 moved 0.545 of the peak); four frames per visit double the workgroups.
-        struct Variant { int form, kb, fchunk; };
-        auto variants_of = [&](int kb, Variant *v) {
-            int n = 0;
-            v[n++] = {0, kb, 0};
-            if (nf == 1 && ctx->apply_wgs_per_cu == 16) {
-                v[n++] = {1, kb, 0};
-                if (ctx->apply_lds_kb <= 0 && kb > 20 && kb <= 28) v[n++] = {1, 20, 0};
-            }
-            if (nf >= 8 && ctx->apply_fchunk <= 0) {
-                const long long live = (long long)cm->blocks_x * cm->blocks_y - (cm->stats_pending ? 0 : (long long)cm->stats[2]);
-                if (live * ((nf + 7) / 8) < 2ll * ctx->num_cus * 7) {
-                    v[n++] = {0, kb, 4};
-                    if (nf >= 16) { v[n++] = {0, kb, 2}; v[n++] = {0, kb, 16}; }     // (twice as many again / one workgroup per block for the whole batch)
-                }
-            }
-            return n;
-        };
-        Variant vtmp[6];
-        if (keep > 1 || variants_of(c_kb[0], vtmp) > 1) {
-            uint8_t *scratch = nullptr;
-            hipEvent_t t0, t1;
-            bool pooled = true;                    // (stream-ordered allocation where the device has a memory pool, plain otherwise)
-            if (hipMallocAsync((void **)&scratch, (size_t)nf * rows * ctx->W, ctx->stream) != hipSuccess) {
-                (void)hipGetLastError();
-                pooled = false;
-                BK_HIP(ctx, hipMalloc((void **)&scratch, (size_t)nf * rows * ctx->W));
-            }
-            BK_HIP(ctx, hipEventCreate(&t0));
-            BK_HIP(ctx, hipEventCreate(&t1));
-            int rc = BK_OK, win = 0;
-            Variant win_v = {0, c_kb[0], 0};
-            float best_ms = -1;
-            // every candidate: one warm-up launch, then a train of launches between two events - back to back, as a caller's
-            // steady state issues them; the globe frames advance through the context's ring from launch to launch, candidate
-            // after candidate, so that none of them is handed the cache state another one left behind
-            // (short launches - stripes, small frames - are timed on longer trains: at 10 us a launch the fixed costs and their
-            //  jitter are as large as the differences looked for)
-            const double work = (double)nf * rows * ctx->W;
-            // (r6: 5 / 3 instead of 2 for the large ones - a train of two 110 us launches picked 128x8 for 4K hammer x16 on one box and
-            //  128x16 on the next, 0.67 against 0.70 of the peak; the tuning runs once per lensmap and kind of launch)
-            const int train = work < 20e6 ? 12 : work < 40e6 ? 6 : work < 300e6 ? 5 : 3;
-            const int span = ctx->nframes > nf ? ctx->nframes - nf + 1 : 1;
-            int seq = 0;
-            // (the cost model's pick is measured LAST: when it wins - the usual case - it is what is compiled at the end, and the map is not
-            //  compiled a third time)
-            float ms_pick = -1;
-            Variant pick_v = {0, c_kb[0], 0};
-            for (int i = keep - 1; i >= 0 && rc == BK_OK; --i) {
-                rc = compile_full(c_rg[i], c_kb[i]);
-                // (timed in the configuration the caller's steady state runs in: with the block map's statistics there - live
-                //  blocks, uneven bands - the launch may take another form than in the first microseconds after a compile)
-                if (rc == BK_OK) rc = coop_stats_wait(ctx, cm);
-                Variant vs[6];
-                const int nv = variants_of(cm->lds_bytes / 1024, vs);
-                for (int k = 0; k < nv && rc == BK_OK; ++k) {
-                    cm->single_form = vs[k].form;
-                    cm->fchunk = vs[k].fchunk;
-                    cm->lds_bytes = clamp_kb(vs[k].kb) * 1024;
-                    rc = launch_compiled(ctx, cm, (seq++ * nf) % span, nf, scratch, ctx->W, (size_t)rows * ctx->W, cm->tinted ? 1 : 0);
-                    if (rc == BK_OK && hipEventRecord(t0, ctx->stream) != hipSuccess) rc = ctx->fail(BK_E_HIP, "block map tuning: hipEventRecord failed");
-                    for (int rep = 0; rep < train && rc == BK_OK; ++rep)
-                        rc = launch_compiled(ctx, cm, (seq++ * nf) % span, nf, scratch, ctx->W, (size_t)rows * ctx->W, cm->tinted ? 1 : 0);
-                    float ms = 0;
-                    if (rc == BK_OK && (hipEventRecord(t1, ctx->stream) != hipSuccess || hipEventSynchronize(t1) != hipSuccess ||
-                                        hipEventElapsedTime(&ms, t0, t1) != hipSuccess))
-                        rc = ctx->fail(BK_E_HIP, "block map tuning: timing failed");
-                    if (g_debug.print_model)
-                        fprintf(stderr, "TUNE %dx%d x%d rg %d kb %d form %d frames per visit %d: %.2f us per launch\n", ctx->W, rows, nf, c_rg[i], vs[k].kb, vs[k].form, vs[k].fchunk ? vs[k].fchunk : 8, ms * 1e3 / train);
-                    if (rc == BK_OK && (best_ms < 0 || ms < best_ms)) { best_ms = ms; win = i; win_v = vs[k]; }
-                    if (rc == BK_OK && i == 0 && k == 0) { ms_pick = ms; pick_v = vs[k]; }
-                }
-                measured = i;
-            }
-            // the first variant of candidate 0 is the cost model's pick: another one replaces it only when it is measurably (3 %) faster
-            if (rc == BK_OK && ms_pick >= 0 && !(best_ms < 0.97f * ms_pick)) { win = 0; win_v = pick_v; }
-            (void)hipEventDestroy(t0);
-            (void)hipEventDestroy(t1);
-            if (pooled) (void)hipFreeAsync(scratch, ctx->stream);
-            else { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(scratch); }
-            if (rc != BK_OK) return rc;
-            best_rg = c_rg[win]; best_kb = win_v.kb;
-            cm->tuned_frames = for_frames;
-            if (win == measured) measured = -1;           // the winner is what is compiled right now
-            else measured = 0;
-            if (measured != -1)
-                if (int r = compile_full(best_rg, best_kb)) return r;
-            measured = -1;
-            cm->single_form = win_v.form;
-            cm->fchunk = win_v.fchunk;
-            cm->lds_bytes = clamp_kb(win_v.kb) * 1024;
+        while (keep < nranked && ranked[keep].cost <= 1.2 * ranked[0].cost) ++keep;
+        file_frames = launch_frames > 0 ? launch_frames : (ctx->nframes >= 16 ? 16 : ctx->nframes >= 8 ? 8 : 1);
+        const int nf = coop_tuning_frames(ctx, file_frames);
+        CoopVariant vtmp[6];
+        if (keep > 1 || coop_variants(ctx, cm, nf, ranked[0].kb, vtmp) > 1) {
+            CoopMeasured m;
+            if (int r = coop_measure(ctx, cm, ranked, keep, nf, &m)) return r;
+            best_rg = ranked[m.win].rg; best_kb = m.v.kb;
+            if (m.win != m.compiled)
+                if (int r = coop_compile_full(ctx, cm, best_rg, best_kb)) return r;
+            winner_compiled = true;
+            cm->single_form = m.v.form;
+            cm->fchunk = m.v.fchunk;
+            cm->lds_bytes = coop_clamp_kb(ctx, m.v.kb) * 1024;
             cm->lds_fixed = true;
-            // (filed under the CALLER's kind of launch: an 8K x 64 launch is measured with the 16 frames a scratch buffer holds, and
-            //  filed under 16 it would be measured again on every launch)
-            CoopMap::Tuned &t = cm->tuned[kind_of(for_frames)];
-            t.rg = best_rg; t.kb = cm->lds_bytes / 1024; t.form = win_v.form; t.fchunk = win_v.fchunk; t.frames = for_frames;
-        } else {                                          // nothing to choose between for this kind: the model's pick, remembered like a measured one
-            CoopMap::Tuned &t = cm->tuned[kind_of(for_frames)];
-            t.rg = best_rg; t.kb = clamp_kb(best_kb); t.form = 0; t.fchunk = 0; t.frames = for_frames;
-            cm->tuned_frames = for_frames;
-        }
+        }                                                 // (else nothing to choose between for this kind: the model's pick, remembered like a measured one)
     }
-    if (measured != -1)
-        if (int r = compile_full(best_rg, best_kb)) return r;
+    if (!winner_compiled)
+        if (int r = coop_compile_full(ctx, cm, best_rg, best_kb)) return r;
+    if (file_frames) coop_tuned_record(cm, file_frames);
     cm->valid = true;
     return BK_OK;
 }
-
-static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, uint8_t *dst, int dst_pitch, size_t frame_stride, int rubix_on);
 
 int launch_apply_coop(bk_ctx *ctx, int frame0, int nframes, uint8_t *dst, int dst_pitch, size_t frame_stride, int rubix_on)
 {
@@ -1372,13 +1498,36 @@ static int coop_launch_lds(bk_ctx *ctx, CoopMap *cm)
 }
 // one-block-per-workgroup grids: take the cost-balanced workgroup -> block map if bands of equal block count are known to be uneven
 // (the block map's statistics arrive asynchronously: until they are here, the direct mapping)
-static bool coop_wants_wgmap(const CoopMap *cm, int kflags) { return !(kflags & (16 | 64)) && !cm->stats_pending && cm->stats[7]; }
+static bool coop_wants_wgmap(const CoopMap *cm, int kflags) { return !(kflags & (BK_AB_ROW_MAJOR | BK_AB_EQUAL_COUNT_BANDS)) && !cm->stats_pending && cm->stats[CS_UNEVEN_BANDS]; }
+
+// The one launch of a kernel with the BK_COOP_KERNEL_ARGS signature over a compiled block map: the launcher chooses the instantiation, the
+// grid and what the launch is about; the block map, the lensmap and the globe are filled in here.
+typedef void (*CoopKernel)(BK_COOP_KERNEL_ARGS);
+static int coop_launch(CoopKernel kernel, bk_ctx *ctx, const CoopMap *cm, dim3 grid, size_t shmem, int globe_frames, int frame0, int nframes,
+                       int fchunk, int lds_buf, uint8_t *dst, int dst_pitch, size_t frame_stride, const uint8_t *pal, int kflags)
+{
+    // (a 64 KiB staging buffer with the palette behind it is more dynamic LDS than a kernel gets unasked)
+    if (shmem > 65536) BK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipLaunchKernelGGL(kernel, grid, dim3(256), shmem, ctx->stream, cm->d_hdr, cm->d_list, cm->d_idx, ctx->d_tints, ctx->d_offsets, ctx->d_globe,
+                       ctx->globe_stride(), globe_frames, frame0, dst, dst_pitch, frame_stride, ctx->W, ctx->rows(), cm->blocks_x,
+                       cm->blocks_x * cm->blocks_y, nframes, fchunk, lds_buf, pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap);
+    BK_HIP(ctx, hipGetLastError());
+    return BK_OK;
+}
+
+// the 8-bit kernel of a launch over blocks of height 8 * RG
+template <int RG>
+static CoopKernel coop_kernel_of(bool rubix, bool once, bool dma, bool wideq)
+{
+    if (rubix) return once ? apply_coop_once_kernel<true, RG> : apply_coop_kernel<true, RG>;
+    if (once) return dma ? apply_coop_once_kernel<false, RG, true> : apply_coop_once_kernel<false, RG>;
+    return wideq ? apply_coop_kernel<false, RG, 6> : apply_coop_kernel<false, RG>;
+}
 
 // the apply launch over an already compiled block map
 static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, uint8_t *dst, int dst_pitch, size_t frame_stride, int rubix_on)
 {
-    const int rows = ctx->rows();
-    const int blocks_x = cm->blocks_x, nblocks = blocks_x * cm->blocks_y;
+    const int nblocks = cm->blocks_x * cm->blocks_y;
     if ((rubix_on != 0) != cm->tinted) return ctx->fail(BK_E_STATE, "apply: the block map is not of this launch's flavour (internal)");
     const int fchunk = coop_frames_per_visit(ctx, cm, nframes);
     const int fblocks = (nframes + fchunk - 1) / fchunk;
@@ -1402,7 +1551,7 @@ static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, ui
         const int by_lds = (int)((160u * 1024u) / (shmem ? shmem : 1));
         const int by_regs = 8;                              // (one-block form: <= 64 VGPRs)
         per_cu = by_lds < by_regs ? (by_lds < 1 ? 1 : by_lds) : by_regs;
-        const int live = cm->stats_pending ? nblocks : nblocks - (int)cm->stats[2];
+        const int live = cm->stats_pending ? nblocks : nblocks - (int)cm->stats[CS_EMPTY_BLOCKS];
         // (up to 1.5 x what is resident the one-block form still wins: 4K panini, 2040 blocks on 1792 places, 9.0 against 9.3 us;
         //  the measured tuning may have settled the form for this block map: CoopMap::single_form)
         if (cm->single_form == 1 || (cm->single_form == 0 && 2 * live <= 3 * ctx->num_cus * per_cu)) per_cu = 1 << 20;         // one block each
@@ -1417,52 +1566,30 @@ static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, ui
     if (wgs_per_band < 1) wgs_per_band = 1;
     if (wgs_per_band > per) wgs_per_band = per;
     dim3 grid((unsigned)(wgs_per_band * 8), (unsigned)fblocks);
-    const bool once = wgs_per_band == per && !(ctx->apply_flags & 32);     // every workgroup has exactly one block (ablation bit 32: persistent form anyway)
+    const bool once = wgs_per_band == per && !(ctx->apply_flags & BK_AB_PERSISTENT);     // every workgroup has exactly one block (BK_AB_PERSISTENT, 32: persistent form anyway)
     int kflags = ctx->apply_flags & ~BK_KF_WGMAP;
     if (once && coop_wants_wgmap(cm, kflags)) kflags |= BK_KF_WGMAP;
     // Single-frame launches fetch the globe chunks non-temporally: between two of them it is the block map L2 should keep
     // (4K hammer 12.4 -> 11.6 us, quincuncial 12.8 -> 11.8, panini 8.4 -> 8.2); batch launches lose 3-10 % that way.
-    // LDS-DMA staging (bit 256) measured neutral (panini 8.39 -> 8.26, hammer 12.42 -> 12.41): the launch is bound by what
-    // crosses the fabric, not by the staging instructions - it stays a developer bit.  Bit 512 leaves both to the caller.
-    if (fchunk == 1 && !(kflags & 512)) kflags |= 128;
-    const bool dma = fchunk == 1 && (kflags & 256) != 0 && !rubix_on;        // (LDS-DMA cannot tint a chunk on its way)
+    // LDS-DMA staging (BK_AB_LDS_DMA, 256) measured neutral (panini 8.39 -> 8.26, hammer 12.42 -> 12.41): the launch is bound by what
+    // crosses the fabric, not by the staging instructions - it stays a developer bit.  BK_AB_NO_AUTO_NT_DMA (512) leaves both to the caller.
+    if (fchunk == 1 && !(kflags & BK_AB_NO_AUTO_NT_DMA)) kflags |= BK_AB_NT_GLOBE;
+    const bool dma = fchunk == 1 && (kflags & BK_AB_LDS_DMA) != 0 && !rubix_on;        // (LDS-DMA cannot tint a chunk on its way)
     // the strided walk with six chunks per thread in registers (82 instead of 64-67 VGPRs: 6 instead of 7 workgroups per CU) only for
     // block maps that have blocks above 16 KiB - the whole-globe lenses, whose staging buffers allow 6 per CU or fewer anyway -
-    // and for batch launches, where the frame pipeline is what it keeps those blocks in (ablation bit 4096: never)
+    // and for batch launches, where the frame pipeline is what it keeps those blocks in (BK_AB_NO_WIDE_PLAN, 4096: never)
     // (4K hammer x16 7.39 -> 7.07 us/frame; mercator, whose 21 KiB buffers let 7 workgroups share a CU, lost 7 % to the registers and keeps
     //  the narrow plan: only where the staging buffer already limits a CU to 6)
-    const bool wideq = !once && !rubix_on && fchunk > 1 && !cm->stats_pending && cm->stats[0] > 1024u && shmem * 7 > 160u * 1024u && !(kflags & 4096);
+    const bool wideq = !once && !rubix_on && fchunk > 1 && !cm->stats_pending && cm->stats[CS_MAX_CHUNKS] > 1024u && shmem * 7 > 160u * 1024u && !(kflags & BK_AB_NO_WIDE_PLAN);
     // (Tried in round 3 and removed: a strided walk in which a block's last frame issues the NEXT block's first globe loads and pixel
     //  addresses - apply_coop_pipe_kernel, git history.  Where it applied (block maps without blocks of more than 1024 chunks) it was
     //  slower - 4K panini at 128x16: 12.0 -> 18.3 us single frame, 4.5 -> 6.4 us/frame x16: 77-96 VGPRs against 67 - and the
     //  whole-globe lenses it was meant for have larger blocks.  What separates mercator's 16.5 us from hammer's 11.5 is not per-block
     //  latency but the quantisation of rounds: 4050 live blocks on 1792 resident places are 2.26 rounds and take 3.)
-    // (a 64 KiB staging buffer with the palette behind it is more dynamic LDS than a kernel gets unasked)
-#define BK_APPLY_K(KERNEL, RBX, N) if (shmem > 65536) BK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL<RBX, N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-                                   hipLaunchKernelGGL((KERNEL<RBX, N>), grid, dim3(256), shmem, ctx->stream, cm->d_hdr, cm->d_list, cm->d_idx, \
-                                           ctx->d_tints, ctx->d_offsets, ctx->d_globe, ctx->globe_stride(), ctx->nframes, frame0, dst,    \
-                                           dst_pitch, frame_stride, ctx->W, rows, blocks_x, nblocks, nframes, fchunk, lds_buf,           \
-                                           ctx->d_pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap)
-#define BK_APPLY_KD(N) hipLaunchKernelGGL((apply_coop_once_kernel<false, N, true>), grid, dim3(256), shmem, ctx->stream, cm->d_hdr, cm->d_list, cm->d_idx, \
-                                           ctx->d_tints, ctx->d_offsets, ctx->d_globe, ctx->globe_stride(), ctx->nframes, frame0, dst,    \
-                                           dst_pitch, frame_stride, ctx->W, rows, blocks_x, nblocks, nframes, fchunk, lds_buf,           \
-                                           ctx->d_pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap)
-#define BK_APPLY_KW(N) hipLaunchKernelGGL((apply_coop_kernel<false, N, 6>), grid, dim3(256), shmem, ctx->stream, cm->d_hdr, cm->d_list, cm->d_idx, \
-                                           ctx->d_tints, ctx->d_offsets, ctx->d_globe, ctx->globe_stride(), ctx->nframes, frame0, dst,    \
-                                           dst_pitch, frame_stride, ctx->W, rows, blocks_x, nblocks, nframes, fchunk, lds_buf,           \
-                                           ctx->d_pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap)
-#define BK_APPLY(N) do { if (once && dma) BK_APPLY_KD(N); else if (once) { BK_APPLY_K(apply_coop_once_kernel, false, N); }             \
-                         else if (wideq) BK_APPLY_KW(N); else { BK_APPLY_K(apply_coop_kernel, false, N); } } while (0)
-#define BK_APPLY_R(N) do { if (once) { BK_APPLY_K(apply_coop_once_kernel, true, N); } else { BK_APPLY_K(apply_coop_kernel, true, N); } } while (0)
-    if (rubix_on) { if (cm->rg == 1) BK_APPLY_R(1); else if (cm->rg == 2) BK_APPLY_R(2); else BK_APPLY_R(4); }
-    else { if (cm->rg == 1) BK_APPLY(1); else if (cm->rg == 2) BK_APPLY(2); else BK_APPLY(4); }
-#undef BK_APPLY_R
-#undef BK_APPLY_K
-#undef BK_APPLY_KD
-#undef BK_APPLY_KW
-#undef BK_APPLY
-    BK_HIP(ctx, hipGetLastError());
-    return BK_OK;
+    const bool rubix = rubix_on != 0;
+    const CoopKernel kernel = cm->rg == 1 ? coop_kernel_of<1>(rubix, once, dma, wideq) : cm->rg == 2 ? coop_kernel_of<2>(rubix, once, dma, wideq)
+                                                                                                     : coop_kernel_of<4>(rubix, once, dma, wideq);
+    return coop_launch(kernel, ctx, cm, grid, shmem, ctx->nframes, frame0, nframes, fchunk, lds_buf, dst, dst_pitch, frame_stride, ctx->d_pal, kflags);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1518,11 +1645,11 @@ int coopmap_traffic_model(bk_ctx *ctx, uint64_t out[8])
     (void)hipFree(bitmap);
     (void)hipFree(counts);
     if (e != hipSuccess) return ctx->fail(BK_E_HIP, "traffic model: %s", hipGetErrorString(e));
-    const uint64_t nblocks = (uint64_t)cm->blocks_x * cm->blocks_y, live = nblocks - cm->stats[2];
+    const uint64_t nblocks = (uint64_t)cm->blocks_x * cm->blocks_y, live = nblocks - cm->stats[CS_EMPTY_BLOCKS];
     out[0] = h[1];
-    out[1] = cm->stats[3];
-    out[2] = cm->stats[4];
-    out[3] = nblocks * sizeof(CoopHdr) + (uint64_t)cm->stats[4] * 4u + live * (uint64_t)(1024 * cm->rg) * 2u;
+    out[1] = cm->stats[CS_LINES];
+    out[2] = cm->stats[CS_CHUNKS];
+    out[3] = nblocks * sizeof(CoopHdr) + (uint64_t)cm->stats[CS_CHUNKS] * 4u + live * (uint64_t)(1024 * cm->rg) * 2u;
     out[4] = h[0];
     out[5] = 8;
     out[6] = nblocks;
@@ -1560,7 +1687,7 @@ int coopmap_band_balance(bk_ctx *ctx, uint32_t out[18])
     BK_HIP(ctx, hipMemcpyAsync(out, cm->d_bands, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     BK_HIP(ctx, hipMemcpyAsync(cum.data(), cm->d_cum, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    out[9] = cm->stats[7] ? 1u : 0u;
+    out[9] = cm->stats[CS_UNEVEN_BANDS] ? 1u : 0u;
     for (int k = 0; k < 8; ++k) {
         const uint32_t a = out[k], b = out[k + 1];
         out[10 + k] = b > a ? cum[b - 1] - (a ? cum[a - 1] : 0u) : 0u;
@@ -1608,8 +1735,8 @@ int coopmap_stats(bk_ctx *ctx, int out[6])
     if (int r = ensure_coopmap(ctx)) return r;
     CoopMap *cm = ctx->coopmap;
     if (int r = coop_stats_wait(ctx, cm)) return r;
-    out[0] = cm->blocks_x * cm->blocks_y; out[1] = cm->slow_blocks; out[2] = (int)cm->stats[2]; out[3] = cm->lds_bytes;
-    out[4] = 8 * cm->rg + 1000 * 128; out[5] = (int)cm->stats[3];
+    out[0] = cm->blocks_x * cm->blocks_y; out[1] = cm->slow_blocks; out[2] = (int)cm->stats[CS_EMPTY_BLOCKS]; out[3] = cm->lds_bytes;
+    out[4] = 8 * cm->rg + 1000 * 128; out[5] = (int)cm->stats[CS_LINES];
     return BK_OK;
 }
 

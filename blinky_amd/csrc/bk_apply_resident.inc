@@ -36,7 +36,6 @@
 #endif
 constexpr int BK_RES_RING = 64;                       // command slots (the host keeps at most half of them in flight)
 constexpr uint32_t BK_RES_FRAME = 1, BK_RES_EXIT = 2;
-constexpr int BK_KF_DIRECT = 1 << 27;              // kflags: commands arrive in the device copies straight from the host (PCIe BAR)
 constexpr int BK_RES_MAX_COPIES = 256, BK_RES_COPY_WORDS = BK_RES_RING * 8;      // device copies of the ring (2 KiB each): 16 pollers per copy
 
 struct ResHost {                                      // pinned, coherent host memory
@@ -342,7 +341,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(res_min_wav
     for (int k = K - 1; k >= 0; --k) if (mode[k] == 1) first = k;
 #pragma unroll
     for (int k = 0; k < K; ++k) if (mode[k] == 1) last = k;
-    bool stream_ok = first < K && !(kflags & 8);   // (ablation bit 8: every frame on its own)
+    bool stream_ok = first < K && !(kflags & BK_RF_SINGLE_FRAMES);   // (developer bit: every frame on its own)
 #pragma unroll
     for (int k = 0; k < K; ++k) if (mode[k] == 2) stream_ok = false;
     if (TAIL && a.depth > K && my[K] >= 0) stream_ok = false;
@@ -353,7 +352,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(res_min_wav
 #define BK_RES_T(J_) (phase + 1u + stride * (J_))
     uint32_t pend1 = 0, pend2 = 0;                 // frames whose stores are all issued: ended 0 / 1 staging barriers ago
     uint32_t n_streamed = 0;                       // (developer statistic) frames that went on into the next without a drain
-    uint32_t busy_ticks = 0;                       // (developer statistic, bit 8192) 100 MHz ticks spent inside frames
+    uint32_t busy_ticks = 0;                       // (developer statistic, BK_RF_WG_TIMING) 100 MHz ticks spent inside frames
     bool have = false;                             // the command of frame seq + 1 is decoded and its first chunks are on their way
     uint32_t peek = 0;                             // wave 0, lanes 0..7: what slot seq + 2 held when frame seq + 1 began
     const uint8_t *gl = a.globe;
@@ -420,7 +419,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(res_min_wav
         if (!tile_empty_) {                                                                                             \
             const int by_ = (BLK_) / a.blocks_x, bx_ = (BLK_) - by_ * a.blocks_x;                                       \
             coop_gather_store<RUBIX, RG, true>(smem, IX_, tile_all_ && aligned, pal_s, dst, 0, dst_pitch, 0, by_ * 8 * RG + ry, \
-                                               bx_ * 128 + cx * 4 * RG, kflags | (aligned4 ? 1024 : 0) | (aligned ? 2048 : 0)); \
+                                               bx_ * 128 + cx * 4 * RG, kflags | (aligned4 ? BK_KF_ALIGNED4 : 0) | (aligned ? BK_KF_ALIGNED16 : 0)); \
         }                                                                                                               \
     } while (0)
 #define BK_RES_RAISE(SEQ_) __hip_atomic_store(a.wg_done + blockIdx.x, (SEQ_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
@@ -463,7 +462,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(res_min_wav
             if (stream_ok && wave == 0) peek = BK_RES_PEEK(BK_RES_T(seq + 1u) - 1u);
         }
         have = false;
-        const long long t_frame0 = (kflags & 8192) ? wall_clock64() : 0;      // (developer bit 8192: time every workgroup's frames)
+        const long long t_frame0 = (kflags & BK_RF_WG_TIMING) ? wall_clock64() : 0;      // (developer bit: time every workgroup's frames)
         const __amdgpu_buffer_rsrc_t rs = BK_RES_RSRC(gl);
         const uint8_t *gl_n = gl;                   // the frame after this one, once its command has been seen (stream_ok only)
         uint8_t *dst_n = dst;
@@ -542,7 +541,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(res_min_wav
 
         // ---- the end of frame seq + 1
         n_streamed += have ? 1u : 0u;
-        if (kflags & 8192) busy_ticks += (uint32_t)(wall_clock64() - t_frame0);
+        if (kflags & BK_RF_WG_TIMING) busy_ticks += (uint32_t)(wall_clock64() - t_frame0);
         if (have) {
             pend1 = BK_RES_T(seq) + stride - 1u;   // its flag is raised two staging barriers from here
             gl = gl_n; dst = dst_n; dst_pitch = pitch_n;
@@ -557,7 +556,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(res_min_wav
         }
         ++seq;
     }
-    if (threadIdx.x == 0) a.wg_up[blockIdx.x] = 0x80000000u | ((kflags & 8192) ? busy_ticks : n_streamed);       // (read by resident_stop for bk_apply_resident_info)
+    if (threadIdx.x == 0) a.wg_up[blockIdx.x] = 0x80000000u | ((kflags & BK_RF_WG_TIMING) ? busy_ticks : n_streamed);       // (read by resident_stop for bk_apply_resident_info)
 #undef BK_RES_ISSUE
 #undef BK_RES_ISSUE_K
 #undef BK_RES_T
@@ -907,13 +906,26 @@ static void res_plan_stride(const std::vector<CoopHdr> &hdr, const std::vector<u
 }
 
 // (re)launch the kernel for the context's current block map
-static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0)
+// force_rg != 0: over blocks of that height (ensure_coopmap's force_rg) - a session growing its blocks, res_relaunch_taller
+static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0, int force_rg = 0);
+
+// the session's block map does not serve it at this block height: compile it twice as tall and launch over that; the map remembers
+// (`grown_rg`) that this height is a session's doing
+static int res_relaunch_taller(bk_ctx *ctx, Resident *R, CoopMap *cm, int shape_tries)
+{
+    cm->valid = false;
+    const int rc = res_launch(ctx, R, shape_tries + 1, cm->rg * 2);
+    if (ctx->coopmap && ctx->coopmap->valid) ctx->coopmap->grown_rg = ctx->coopmap->rg;
+    return rc;
+}
+
+static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries, int force_rg)
 {
     // a session outlives resident_quiesce: after a bk_resize / bk_set_rows / failed bk_build in between there may be no lensmap (or
     // no rows) to compile a block map from - say so instead of launching on freed tables (bk_apply_device's answer to the same state)
     if (!ctx->lensmap_valid || !ctx->d_offsets || ctx->W <= 0 || ctx->rows() <= 0 || ctx->apply_variant == 0)
         return ctx->fail(BK_E_STATE, "resident apply: no lensmap for the current size / rows (bk_build or bk_set_lensmap first)");
-    if (int r = ensure_coopmap(ctx, 1, R->rubix ? 1 : 0)) return r;
+    if (int r = ensure_coopmap(ctx, 1, R->rubix ? 1 : 0, force_rg)) return r;
     CoopMap *cm = ctx->coopmap;
     if (int r = coop_stats_wait(ctx, cm)) return r;
     const int nblocks = cm->blocks_x * cm->blocks_y;
@@ -931,16 +943,16 @@ static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0)
     R->form = 1;
     // the staging buffer holds the largest listed block of the map (the launch-per-frame kernel may run with a smaller one and
     // take such blocks in passes; here they would fall to the direct gather)
-    int lds_buf = (int)std::min<uint32_t>(cm->stats[0], BK_COOP_MAX_CHUNKS + 1) * 16;
+    int lds_buf = (int)std::min<uint32_t>(cm->stats[CS_MAX_CHUNKS], BK_COOP_MAX_CHUNKS + 1) * 16;
     lds_buf = std::max(1024, (lds_buf + 1023) & ~1023);
     const size_t shmem = (size_t)lds_buf + (R->rubix ? BK_PAL_BYTES : 0);
     ResArgs a;
     a.hdr = cm->d_hdr; a.list = cm->d_list; a.idx = cm->d_idx; a.tint_t = ctx->d_tints; a.lmap = ctx->d_offsets;
     a.globe = ctx->d_globe; a.globe_stride = ctx->globe_stride(); a.globe_frames = ctx->nframes;
     a.W = ctx->W; a.rows = ctx->rows(); a.blocks_x = cm->blocks_x; a.nblocks = nblocks; a.lds_buf = lds_buf;
-    a.pal = R->d_pal; a.kflags = ctx->apply_flags & (4 | 8 | 8192);       // (+ BK_KF_DIRECT below)   // (developer bits: 4 no stores, 8 every frame on its own, 8192 time every workgroup's frames)
+    a.pal = R->d_pal; a.kflags = ctx->apply_flags & BK_RF_KERNEL_MASK;       // (+ BK_KF_DIRECT below; the mask: see BkResidentFlag)
     a.rh = R->h; a.idle_ticks = (uint32_t)std::min(4.0e9, R->idle_ms * 1e5);
-    const int nq = cm->stats[0] > 1024u ? 6 : 4;
+    const int nq = cm->stats[CS_MAX_CHUNKS] > 1024u ? 6 : 4;
     // The smallest form whose grid holds every block of the map on the chip: one, two or three blocks per workgroup with their chunk
     // offsets in registers; if the map needs more, blocks twice as tall first (a workgroup's frame time goes with the NUMBER of its
     // blocks - one trip to memory each, measured 2.5 us - so the same screen in taller blocks is less work: 4K mercator at 128 x 16 is
@@ -949,7 +961,7 @@ static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0)
     // per workgroup resident and fetches the rest of its block map per frame, as a launch would.
     int K = 1, places = 0;
     ResPlan plan;
-    const uint32_t tab_row = std::min<uint32_t>((cm->stats[0] + 255u) & ~255u, (uint32_t)nq * 256u) * 4u;      // bytes of table per block, worst case
+    const uint32_t tab_row = std::min<uint32_t>((cm->stats[CS_MAX_CHUNKS] + 255u) & ~255u, (uint32_t)nq * 256u) * 4u;      // bytes of table per block, worst case
     auto form_shmem = [&](int form) -> size_t { return shmem + (form == 4 || form == 6 || form == 8 ? (size_t)form * tab_row : form == 10 ? 8 * (size_t)tab_row : 0); };
     auto try_form = [&](int form, int depth_cap, bool *ok) -> int {
         *ok = false;
@@ -964,24 +976,16 @@ static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0)
     // (r6: ... and not from a map that a session's growth produced already - `grown_rg`: the next session of the same lensmap used to find
     //  session 1's 128 x 16 map, grow it once more and take a form session 1 had not even looked at: 4K gumby 14.9 us per frame in the first
     //  session, 35.5 in every later one, 256 workgroups of eight 128 x 32 blocks each)
-    const bool may_grow = rg < 4 && shape_tries < 2 && !(ctx->tile_shape == 1 || ctx->tile_shape == 2 || ctx->tile_shape == 4) && cm->grown_rg != rg;
+    const bool may_grow = rg < 4 && shape_tries < 2 && !coop_forced_rg(ctx, force_rg) && cm->grown_rg != rg;
     {
         for (int form : {1, 2, 3}) {
-            if (form == 1 && (nq > 4 || (ctx->apply_flags & 2048))) continue;         // (developer bit 2048: not the one-block form)
+            if (form == 1 && (nq > 4 || (ctx->apply_flags & BK_RF_NO_ONE_BLOCK))) continue;
             K = form;
             if (int r = try_form(form, form, &ok)) return r;
             if (ok) break;
         }
-        if (!ok && may_grow) {
-            const int keep = ctx->tile_shape;
-            ctx->tile_shape = rg * 2;
-            cm->valid = false;
-            const int rc = res_launch(ctx, R, shape_tries + 1);
-            ctx->tile_shape = keep;
-            if (ctx->coopmap && ctx->coopmap->valid) ctx->coopmap->grown_rg = ctx->coopmap->rg;
-            return rc;
-        }
-        if (!ok && !(ctx->apply_flags & 4096) && !R->rubix)                           // (developer bit 4096: no table forms)
+        if (!ok && may_grow) return res_relaunch_taller(ctx, R, cm, shape_tries);
+        if (!ok && !(ctx->apply_flags & BK_RF_NO_TABLES) && !R->rubix)
             for (int form : {4, 6, 8}) {
                 K = form;
                 if (int r = try_form(form, form, &ok)) return r;
@@ -992,7 +996,7 @@ static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0)
             // leaves less of the map to fetch
             ResPlan p10; int places10 = 0; bool ok10 = false;
             K = 10;
-            if (!(ctx->apply_flags & 4096) && !R->rubix) { if (int r = try_form(10, 0, &ok10)) return r; }
+            if (!(ctx->apply_flags & BK_RF_NO_TABLES) && !R->rubix) { if (int r = try_form(10, 0, &ok10)) return r; }
             p10 = plan; places10 = places;
             bool ok9 = false;
             K = 9;
@@ -1007,7 +1011,7 @@ static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0)
     // at a time is not faster for it (a frame is still one trip per block), pipelined submissions are: `stride` frames side by side.
     int stride = 1;
     plan.phase.assign((size_t)plan.grid, 0);
-    if (K >= 1 && K <= 8 && !(ctx->apply_flags & 16) && plan.grid > 9) {                  // (developer bit 16 of the resident flags: no stride)
+    if (K >= 1 && K <= 8 && !(ctx->apply_flags & BK_RF_NO_STRIDE) && plan.grid > 9) {
         const int per_group = ((int)order.size() + K - 1) / K;              // workers one copy of the map needs at K blocks each
         const int room = (places - 1) / std::max(1, per_group);
         for (int st = std::min(8, room); st >= 2; --st) {
@@ -1019,15 +1023,8 @@ static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0)
     // ... and a map of one block per workgroup that just fits (1080p hammer at 128 x 8: 1530 blocks on 2048 places) has no room for a
     // second copy: blocks twice as tall are half as many, a trip to memory is hardly longer for them, and the stride doubles - 3.6 us per
     // pipelined frame at 128 x 8, 1.35 at 128 x 32 with five frames side by side (stereographic, measured)
-    if (stride == 1 && K == 1 && may_grow && (int)order.size() * 2 > places && (int)order.size() > 64) {
-        const int keep = ctx->tile_shape;
-        ctx->tile_shape = rg * 2;
-        cm->valid = false;
-        const int rc = res_launch(ctx, R, shape_tries + 1);
-        ctx->tile_shape = keep;
-        if (ctx->coopmap && ctx->coopmap->valid) ctx->coopmap->grown_rg = ctx->coopmap->rg;
-        return rc;
-    }
+    if (stride == 1 && K == 1 && may_grow && (int)order.size() * 2 > places && (int)order.size() > 64)
+        return res_relaunch_taller(ctx, R, cm, shape_tries);
     const int grid = plan.grid;
     R->plan_assign = plan.assign;
     R->plan_hdr_chunks.resize(hdr.size());
@@ -1052,7 +1049,7 @@ static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0)
             fprintf(stderr, "RESIDENT plan XCD %d: %d workers, %d blocks, chunks per worker mean %.0f max %.0f\n", x, xn, xb, xn ? xs / xn : 0.0, xm);
         }
         fprintf(stderr, "RESIDENT plan: %u live blocks (max %u chunks, %d above 1024, %d above 1536), grid %d depth %d K %d nq %d lds %d, cost per workgroup mean %.0f max %.0f\n",
-                nlive, cm->stats[0], big4, big, grid, plan.depth, K, nq, lds_buf, nw ? sum / nw : 0.0, mx);
+                nlive, cm->stats[CS_MAX_CHUNKS], big4, big, grid, plan.depth, K, nq, lds_buf, nw ? sum / nw : 0.0, mx);
     }
     if (grid > R->cap_wg) {
         (void)hipFree(R->d_done); (void)hipFree(R->d_up);
@@ -1107,7 +1104,7 @@ static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0)
             if (int r = res_drain(ctx, R, true)) return r;
             if (R->shrink >= 6) return ctx->fail(BK_E_HIP, "resident apply: only %u of %d workgroups became resident", up, grid);
             ++R->shrink;
-            return res_launch(ctx, R, shape_tries);
+            return res_launch(ctx, R, shape_tries, force_rg);
         }
     }
     return BK_OK;

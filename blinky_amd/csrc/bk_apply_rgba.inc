@@ -329,33 +329,20 @@ int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst, int ds
     if (int r = ensure_coopmap(ctx, planes, rubix ? 1 : 0)) return r;
     CoopMap *cm = ctx->coopmap;
     if (rubix != cm->tinted) return ctx->fail(BK_E_STATE, "truecolour apply: the block map is not of this launch's flavour (internal)");
-    const int blocks_x = cm->blocks_x, nblocks = blocks_x * cm->blocks_y;
+    const int nblocks = cm->blocks_x * cm->blocks_y;
     // planes per block visit as an 8-bit launch of that many frames has them; a visit serves whole truecolour frames
     const int fchunk = std::max(1, coop_frames_per_visit(ctx, cm, planes) / 4);
     const int fblocks = (nframes + fchunk - 1) / fchunk;
     const int per = (nblocks + 7) / 8;
     const int lds_buf = coop_launch_lds(ctx, cm);
-    // Of the developer ablations (ctx->apply_flags, bk_debug_set_ablation) this kernel knows one: bit 16, the row-major walk its
+    // Of the developer ablations (ctx->apply_flags, bk_debug_set_ablation) this kernel knows one: BK_AB_ROW_MAJOR, the row-major walk its
     // bk_block_at call honours.  The others switch parts of the 8-bit kernels this one does not have (forms, DMA staging, the
     // pipelining, stores off ...) and are deliberately not passed on.
-    int kflags = ctx->apply_flags & 16;
+    int kflags = ctx->apply_flags & BK_AB_ROW_MAJOR;
     if (coop_wants_wgmap(cm, ctx->apply_flags)) kflags |= BK_KF_WGMAP;
     const dim3 grid((unsigned)(per * 8), (unsigned)fblocks);
-#define BK_APPLY_RGBA(N, RBX) if (RBX && lds_buf + BK_PAL_BYTES > 65536)                                                                                 \
-                                  BK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(BK_RGBA_KERNEL_##RBX<N>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                                  lds_buf + BK_PAL_BYTES));                                                                \
-                              hipLaunchKernelGGL((BK_RGBA_KERNEL_##RBX<N>), grid, dim3(256), (size_t)lds_buf + (RBX ? BK_PAL_BYTES : 0), ctx->stream, \
-                                            cm->d_hdr, cm->d_list, cm->d_idx,                                                                  \
-                                            ctx->d_tints, ctx->d_offsets, ctx->d_globe, ctx->globe_stride(), ctx->nframes / 4, globe0, dst,       \
-                                            dst_pitch, frame_stride, ctx->W, rows, blocks_x, nblocks, nframes, fchunk, lds_buf,               \
-                                            RBX ? d_lut : ctx->d_pal, kflags, cm->d_order, cm->d_bands, cm->d_wgmap)
-#define BK_RGBA_KERNEL_true apply_coop_rgba_tinted_kernel
-#define BK_RGBA_KERNEL_false apply_coop_rgba_kernel
-    if (rubix) { if (cm->rg == 1) { BK_APPLY_RGBA(1, true); } else if (cm->rg == 2) { BK_APPLY_RGBA(2, true); } else { BK_APPLY_RGBA(4, true); } }
-    else { if (cm->rg == 1) { BK_APPLY_RGBA(1, false); } else if (cm->rg == 2) { BK_APPLY_RGBA(2, false); } else { BK_APPLY_RGBA(4, false); } }
-#undef BK_RGBA_KERNEL_true
-#undef BK_RGBA_KERNEL_false
-#undef BK_APPLY_RGBA
-    BK_HIP(ctx, hipGetLastError());
-    return BK_OK;
+    const CoopKernel kernel = rubix ? (cm->rg == 1 ? apply_coop_rgba_tinted_kernel<1> : cm->rg == 2 ? apply_coop_rgba_tinted_kernel<2> : apply_coop_rgba_tinted_kernel<4>)
+                                    : (cm->rg == 1 ? apply_coop_rgba_kernel<1> : cm->rg == 2 ? apply_coop_rgba_kernel<2> : apply_coop_rgba_kernel<4>);
+    return coop_launch(kernel, ctx, cm, grid, (size_t)lds_buf + (rubix ? BK_PAL_BYTES : 0), ctx->nframes / 4, globe0, nframes, fchunk, lds_buf, dst,
+                       dst_pitch, frame_stride, rubix ? d_lut : ctx->d_pal, kflags);
 }

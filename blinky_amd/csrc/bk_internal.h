@@ -135,6 +135,9 @@ struct bk_ctx {
     int apply_variant = -1;          // -1 auto (= 2); 0 direct gather, 2 workgroup-cooperative LDS blocks
     int num_cus = 256;               // multiProcessorCount of the device
     int apply_flags = 0;             // developer ablations of the coop apply (bk_debug_set_ablation): 2 no globe loads, 4 no stores, 8 no load pipelining
+                                     // ... (BkAblation, bk_apply_coop.hip).  A resident session reads the same word its own way (BkResidentFlag):
+                                     // 4 no stores, 8 every frame on its own, 16 no frame stride, 2048 not the one-block form, 4096 no table
+                                     // forms, 8192 time every workgroup's frames; its kernel is handed 4 | 8 | 8192 of them and nothing else
     int apply_block_cost = -1;       // coop apply: constant term of a block's cost in the band balance (-1 = default; knob 600+n)
     int apply_lds_kb = 0;            // coop apply: force the staging buffer size in KiB (0 = cost model; knob 400+n)
     int apply_fchunk = 0;            // frames a workgroup keeps a block for (0 = default 8; knob 300+n)

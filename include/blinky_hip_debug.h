@@ -37,7 +37,10 @@ int         bk_debug_forward_tiles(bk_ctx *ctx, int *taken, int *total);
  * cost, 128 non-temporal globe loads, 256 LDS-DMA staging (global_load_lds) in single-frame launches of the one-block form,
  * 512 no automatic choice of 128 / 256 for single-frame launches, 2048 __syncthreads() instead of the raw LDS barriers, 4096 never
  * the six-chunks-per-thread register plan of the strided walk - results stay exact for 8..4096); results are wrong while
- * bits 2/4 are set.  0 restores normal operation. */
+ * bits 2/4 are set.  0 restores normal operation.
+ * A resident session (bk_apply_resident_begin) reads the same word in its own way: 4 no stores, 8 every frame on its own, 16 no frame
+ * stride, 2048 never the one-block form, 4096 no table forms, 8192 time every workgroup's frames; its kernel is handed bits 4, 8 and
+ * 8192 only, the others steer its launcher.  The truecolour launches know bit 16 alone.  65536: rubix launches stage without the tint. */
 int         bk_debug_set_ablation(bk_ctx *ctx, int bits);
 /* staged apply statistics of the current lensmap: out = {blocks, blocks on the direct-gather fallback,
  * empty blocks, bytes of one LDS staging buffer, 128000 + block height in pixels, 128-byte lines staged per frame} */
