@@ -695,13 +695,19 @@ extern "C" int bk_apply_device(bk_ctx *ctx, int frame0, int nframes, void *dst_d
     return bk::launch_apply(ctx, frame0, nframes, first, dst_pitch, frame_stride, rubix_on);
 }
 
-// what bk_apply_rgba_device and bk_apply_rgba_tinted_device check alike; `who` names the entry point in the message
-static int rgba_apply_args(bk_ctx *ctx, const char *who, int globe0, int nframes, const void *dst_dev, int dst_pitch, size_t frame_stride, int x0, int y0)
+// what bk_apply_rgba_device, bk_apply_rgba_tinted_device and bk_apply_rgba_ss2_device check alike; `who` names the entry point in the
+// message; ss2: the frames are (W + 1) / 2 pixels wide, and the owned rows must be whole row pairs
+static int rgba_apply_args(bk_ctx *ctx, const char *who, int globe0, int nframes, const void *dst_dev, int dst_pitch, size_t frame_stride, int x0, int y0,
+                           bool ss2 = false)
 {
     if (ctx->device < 0) return ctx->fail(BK_E_STATE, "%s: this context was created without a device (BK_DEVICE_NONE)", who);
     if (!ctx->lensmap_valid) return ctx->fail(BK_E_STATE, "%s: no lensmap (bk_build / bk_set_lensmap first)", who);
-    if (x0 < 0 || y0 < 0 || globe0 < 0 || nframes < 1 || (long long)dst_pitch < 4ll * ((long long)ctx->W + x0))
+    const long long width = ss2 ? ((long long)ctx->W + 1) / 2 : (long long)ctx->W;
+    if (x0 < 0 || y0 < 0 || globe0 < 0 || nframes < 1 || (long long)dst_pitch < 4ll * (width + x0))
         return ctx->fail(BK_E_INVALID, "%s: bad pitch/origin/frames", who);
+    if (ss2 && ((ctx->row0 & 1) || ((ctx->row1 & 1) && ctx->row1 != ctx->H)))
+        return ctx->fail(BK_E_STATE, "%s: the owned rows [%d, %d) cut a 2x2 quad: row0 must be even and row1 even or the frame's height (bk_set_rows)", who,
+                         ctx->row0, ctx->row1);
     if (((uintptr_t)dst_dev | (uintptr_t)dst_pitch | (uintptr_t)frame_stride) & 3u)
         return ctx->fail(BK_E_INVALID, "%s: dst, pitch and frame stride must be multiples of 4 bytes", who);
     if (ctx->nframes < 4) return ctx->fail(BK_E_STATE, "%s: a truecolour globe is four ring slots (bk_set_frames(4 * globes))", who);
@@ -745,6 +751,21 @@ extern "C" int bk_apply_rgba_tinted_device(bk_ctx *ctx, int globe0, int nframes,
     if (int r = upload_lut_rgba(ctx, lut)) return r;
     uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
     return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride, ctx->d_lut_rgba);
+}
+
+// 2x2 supersampling of the truecolour apply: the lensmap is W x H, the frames written are (W + 1) / 2 x (H + 1) / 2, every pixel the
+// rounded mean of its mapped samples; lut == NULL: the samples of bk_apply_rgba_device, else those of bk_apply_rgba_tinted_device
+extern "C" int bk_apply_rgba_ss2_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch, size_t frame_stride, int x0, int y0,
+                                        const uint8_t lut[4][BK_MAX_PLATES][256])
+{
+    if (!ctx || !dst_dev) return BK_E_INVALID;
+    if (int r = rgba_apply_args(ctx, "bk_apply_rgba_ss2_device", globe0, nframes, dst_dev, dst_pitch, frame_stride, x0, y0, true)) return r;
+    if (int r = ensure_device(ctx)) return r;                // (ends a resident session)
+    bk::Range range("bk_apply_rgba_ss2_device");
+    if (lut)
+        if (int r = upload_lut_rgba(ctx, lut)) return r;
+    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0 / 2) * dst_pitch + (size_t)x0 * 4;
+    return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride, lut ? ctx->d_lut_rgba : nullptr, true);
 }
 
 // ---- resident single-frame apply (bk_apply_resident.inc) ------------------------------------------------------------

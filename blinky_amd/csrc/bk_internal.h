@@ -215,9 +215,10 @@ void coopmap_invalidate(bk_ctx *ctx);
 int launch_apply_coop(bk_ctx *ctx, int frame0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch,
                       size_t frame_stride, int rubix_on);
 // bk_apply_rgba.inc (part of bk_apply_coop.hip): truecolour frames from truecolour globes (four ring slots each);
-// d_lut = nullptr: the plain launch, else the tinted one through the device copy of uint8 [4][BK_MAX_PLATES][256]
+// d_lut = nullptr: the plain launch, else the tinted one through the device copy of uint8 [4][BK_MAX_PLATES][256];
+// ss2: 2x2 supersampling into half-size frames (bk_apply_rgba_ss2_device) - dst is then row row0 / 2 of the half-size frame
 int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch, size_t frame_stride,
-                      const uint8_t *d_lut = nullptr);
+                      const uint8_t *d_lut = nullptr, bool ss2 = false);
 int coopmap_stats(bk_ctx *ctx, int out[6]);   // blocks, direct-gather blocks, empty blocks, LDS bytes per buffer
 int coopmap_traffic_model(bk_ctx *ctx, uint64_t out[8]);
 int coopmap_xcd_probe(bk_ctx *ctx, int *out, int nwg);

@@ -77,6 +77,7 @@ _SIGS = {
     "bk_upload_plate_rgba_device": (_i, [_vp, _i, _i, _vp, _i]),
     "bk_apply_rgba_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i]),
     "bk_apply_rgba_tinted_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
+    "bk_apply_rgba_ss2_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
     "bk_globe_device_ptr": (_vp, [_vp, _i]),
     "bk_fill_plate_lcg": (_i, [_vp, _i, _i, C.c_uint32]),
     "bk_apply": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
@@ -454,6 +455,16 @@ class Context:
             if lut.shape != (4, MAX_PLATES, 256):
                 raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
         self._chk(lib.bk_apply_rgba_tinted_device(self._h, globe0, nframes, dst_ptr, pitch, frame_stride, x0, y0, _ptr(lut)))
+
+    def apply_rgba_ss2_device(self, dst_ptr, pitch, frame_stride, globe0=0, nframes=1, x0=0, y0=0, lut=None):
+        """2x2 supersampling: the context is W x H, the frames written are (W + 1) // 2 x (H + 1) // 2 truecolour pixels, each the
+        rounded mean of its mapped samples; lut None: the samples of apply_rgba_device, else of apply_rgba_tinted_device through
+        lut (uint8 [4][6][256]).  pitch / frame_stride in bytes and x0 / y0 in pixels of the half-size frames"""
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8)
+            if lut.shape != (4, MAX_PLATES, 256):
+                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        self._chk(lib.bk_apply_rgba_ss2_device(self._h, globe0, nframes, dst_ptr, pitch, frame_stride, x0, y0, _ptr(lut)))
 
     # ---- the resident single-frame apply (bk_apply_resident_*): one kernel stays on the device, frames are commands
     def resident_begin(self, rubix_on=False, pal=None, idle_ms=0.0):

@@ -21,7 +21,7 @@
  *   - there is no CPU fallback: without a usable GPU bk_create fails.
  *   - texels and pixels are 8-bit palettised, as the reference's (TyrQuake's software rasteriser).  TRUECOLOUR - 32-bit plates
  *     warped into 32-bit frames, for hosts whose plates are frame buffers of a present-day renderer - is bk_upload_plate_rgba /
- *     bk_upload_plate_rgba_device / bk_apply_rgba_device / bk_apply_rgba_tinted_device: a 32-bit globe is four byte planes in four consecutive slots of the same
+ *     bk_upload_plate_rgba_device / bk_apply_rgba_device / bk_apply_rgba_tinted_device / bk_apply_rgba_ss2_device: a 32-bit globe is four byte planes in four consecutive slots of the same
  *     globe ring, so lens build, lensmap and everything else in this header are shared with the 8-bit path as they are.
  */
 #ifndef BLINKY_HIP_H
@@ -261,7 +261,7 @@ int bk_apply_device(bk_ctx *ctx, int frame0, int nframes, void *dst_dev, int dst
  * Rubix tints on truecolour frames: bk_apply_rgba_tinted_device below.
  * Out of scope: the resident kernel; a host-pointer bk_apply_rgba; the bk_comm_* / bk_multi_*
  * exchanges, whose stripe buffers are W bytes per row (stripe CONTEXTS - bk_set_rows - do work); the drop-in fisheye_hip.c, whose
- * engine is 8-bit; texel filtering (nearest texel, as everywhere). */
+ * engine is 8-bit; texel filtering: every pixel is one nearest texel - antialiased frames are bk_apply_rgba_ss2_device below. */
 int bk_apply_rgba_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch,
                          size_t frame_stride, int x0, int y0);
 /* bk_apply_rgba_tinted_device: f_rubix on truecolour frames.  The reference tints a plate's palette (create_palmap, fisheye.c:857-908:
@@ -276,9 +276,33 @@ int bk_apply_rgba_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, in
  * same; it is apart from the 8-bit palette's, so 8-bit rubix launches and truecolour ones alternate without uploads.
  * The launch runs over the TINTED block map (both flavours are kept: alternating with plain launches swaps, it does not recompile).
  * Out of scope: the resident kernel; a host-pointer call; the bk_comm_* / bk_multi_* exchanges; the drop-in fisheye_hip.c; texel
- * filtering; tints of different strength per pixel - beyond what a caller's own tables express. */
+ * filtering (one nearest texel per pixel; bk_apply_rgba_ss2_device below supersamples tinted frames too); tints of different strength per pixel - beyond what a caller's own tables express. */
 int bk_apply_rgba_tinted_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch,
                                 size_t frame_stride, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256]);
+/* bk_apply_rgba_ss2_device: antialiased truecolour frames by 2x2 SUPERSAMPLING, fused into the apply.  The context is sized, built and
+ * filled exactly as for bk_apply_rgba_device, at the SUPERSAMPLED size W x H - this is supersampling of the whole pipeline, the
+ * renderer's plates included: they are min(W, H) texels - and the call writes frames of Wo = (W + 1) / 2 by Ho = (H + 1) / 2 32-bit
+ * pixels: what bk_apply_rgba_device (lut == NULL) or bk_apply_rgba_tinted_device (lut != NULL) would write into a W x H frame,
+ * averaged over 2x2 quads with a box filter, without that frame ever being stored.
+ * Semantics (exact, integer): for output pixel (X, Y) of frame f let S be the samples (2X+i, 2Y+j), i, j in {0, 1}, that lie inside
+ * W x H and whose lensmap entry is not NULL, and n = |S|.  n == 0: the pixel is left untouched.  n > 0: byte c is
+ * (sum over S of v_c(s) + n/2) / n in integer arithmetic (n/2 = 0, 1, 1, 2), v_c(s) being the byte the full-size call would store for
+ * sample s; a tint is applied per sample, before the average.  All four bytes are treated alike - they are opaque, as everywhere here.
+ * Addressing: output pixel (X, Y) of frame f lands at dst + f*frame_stride + (y0+Y)*dst_pitch + 4*(x0+X), frame f warped from
+ * truecolour globe (globe0 + f) % (resident slots / 4); dst_pitch, frame_stride, x0, y0 are the half-size frames'.  A context that owns
+ * rows [row0, row1) (bk_set_rows) writes output rows [row0/2, (row1+1)/2): row0 must be even and row1 even or H - a quad must not
+ * straddle two contexts - otherwise BK_E_STATE.
+ * Alignment: as bk_apply_rgba_device (multiples of 4 required); with dst + 4 * x0, dst_pitch and frame_stride multiples of 16 fully
+ * mapped tiles leave as 8- or 16-byte stores that fill whole 128-byte lines.  BK_E_INVALID / BK_E_STATE: the cases of
+ * bk_apply_rgba_device with Wo in the pitch test, dst_pitch >= 4 * (Wo + x0).  Asynchronous on the context's stream; ends a resident
+ * session.  The launch is bk_apply_rgba_device's / bk_apply_rgba_tinted_device's in everything but the kernel - same block maps, same
+ * tuning, same LUT copy - so alternating with them or with 8-bit launches swaps and recompiles nothing more than they do among themselves.
+ * It reads what the full-size launch reads and stores a quarter of its bytes (measured: profiles/rgba_ss2_apply.txt).
+ * Out of scope: the resident kernel; a host-pointer call; the bk_comm_* / bk_multi_* exchanges; factors other than 2; filters other than
+ * the box (bilinear texel filtering would need fractional texel coordinates from the lens build). */
+int bk_apply_rgba_ss2_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch,
+                             size_t frame_stride, int x0, int y0,
+                             const uint8_t lut[4][BK_MAX_PLATES][256] /* nullable: NULL = plain, else tinted */);
 
 /* ---- resident single-frame apply ------------------------------------------------------------------------------------
  * replaces: the per-frame call of render_lensmap (fisheye.c:803 -> 2406-2424) for hosts whose globes stay in device memory.

@@ -7,14 +7,20 @@ At 3840x2160 cube/panini and cube/hammer, over the 64-slot LCG ring of the bench
 B's output is compared with A's plane by plane before anything is timed.  Timing: HIP events on the context's stream, warm-up
 launches first, regions of at least --region seconds made of ten event-timed trains of launches (a region's figure is the median
 train), A / B / A / B ... alternated --repeats times inside this one process.  The target: B's median <= A's median + A's own spread
-(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE]
+(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2]
 
 --tint: the same protocol for f_rubix on truecolour frames, three launches alternated A' / B' / B:
   A'  one bk_apply_device launch of 64 8-bit frames with rubix_on = 1 (existing code: the same bytes through the same number of LUT
       passes per chunk)
   B'  one bk_apply_rgba_tinted_device launch of 16 truecolour frames with lut[c] = that same palette for all four c
   B   the plain truecolour launch
-B' must equal A' plane by plane before anything is timed.  The target: B''s median <= A''s median + A''s own spread."""
+B' must equal A' plane by plane before anything is timed.  The target: B''s median <= A''s median + A''s own spread.
+
+--ss2 [--tint]: the same protocol for the fused 2x2 supersampling, on one context at the supersampled size, A / B alternated:
+  A  one bk_apply_rgba_device (--tint: bk_apply_rgba_tinted_device) launch of 16 full-size truecolour frames
+  B  one bk_apply_rgba_ss2_device launch over the same globes (--tint: through the same tables) into 16 half-size frames
+B must equal the numpy average of A's full-size output (mapped samples only, (sum + n // 2) // n) before anything is timed.  B reads
+what A reads and stores a quarter of its bytes; the expectation: B's median <= A's median + A's own spread."""
 import argparse
 import json
 import os
@@ -154,6 +160,83 @@ def measure_tint(lens, repeats, region_s):
                 target_met=bool(med_t <= med_a + spread))
 
 
+def measure_ss2(lens, repeats, region_s, tint):
+    ctx = blinky_amd.Context(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_frames(SLOTS)
+    S.configure(ctx, "cube", lens, None, (W, H))
+    ctx.build()
+    for f in range(SLOTS):
+        for p in range(6):
+            ctx.fill_plate_lcg(f, p, seed_frame=f)
+    lut = None
+    if tint:
+        pal = blinky_amd.ffi.create_palmap(((np.arange(768) * 37) % 256).astype(np.uint8))
+        lut = np.ascontiguousarray(np.broadcast_to(pal, (4, 6, 256)))
+    F, Wo, Ho = SLOTS // 4, (W + 1) // 2, (H + 1) // 2
+    out_a = torch.zeros((F, H, W, 4), dtype=torch.uint8, device="cuda")
+    out_b = torch.zeros((F, Ho, Wo, 4), dtype=torch.uint8, device="cuda")
+
+    def a():
+        if tint:
+            ctx.apply_rgba_tinted_device(out_a.data_ptr(), 4 * W, 4 * W * H, lut, globe0=0, nframes=F)
+        else:
+            ctx.apply_rgba_device(out_a.data_ptr(), 4 * W, 4 * W * H, globe0=0, nframes=F)
+
+    def b():
+        ctx.apply_rgba_ss2_device(out_b.data_ptr(), 4 * Wo, 4 * Wo * Ho, globe0=0, nframes=F, lut=lut)
+
+    for _ in range(3):                                     # warm-up: the first launch compiles and tunes the block map both share
+        a()
+        b()
+    torch.cuda.synchronize()
+    # B against the numpy average of A at full size: unmapped samples do not count, quads without a mapped sample stay as they were (0)
+    off, _ = ctx.read_lensmap()
+    mapped = (np.asarray(off).reshape(H, W) != 0xFFFFFFFF)
+    del off
+    n = mapped.reshape(Ho, 2, Wo, 2).sum(axis=(1, 3), dtype=np.uint32)
+    div = np.maximum(n, 1)[:, :, None]
+    for f in range(F):
+        full = out_a[f].cpu().numpy().astype(np.uint32) * mapped[:, :, None]
+        want = ((full.reshape(Ho, 2, Wo, 2, 4).sum(axis=(1, 3), dtype=np.uint32) + (n // 2)[:, :, None]) // div).astype(np.uint8)
+        want[n == 0] = 0
+        got = out_b[f].cpu().numpy()
+        if not np.array_equal(got, want):
+            raise SystemExit(f"{lens}: supersampled frame {f} differs from the average of the full-size frame in {int((got != want).sum())} bytes - nothing timed")
+    del full, want, got
+    pilot = min(region(stream, a, 4, trains=3), region(stream, b, 4, trains=3))
+    per_train = max(2, int(region_s / 10 / pilot) + 1)
+    ra, rb = [], []
+    for _ in range(repeats):
+        ra.append(region(stream, a, per_train))
+        rb.append(region(stream, b, per_train))
+    st = ctx.tile_stats()
+    ctx.close()
+    med_a, med_b, spread = statistics.median(ra), statistics.median(rb), max(ra) - min(ra)
+    return dict(lens=lens, W=W, H=H, tint=bool(tint), block=f"128x{st['tile_h'] % 1000}", lds_kib=st["lds_bytes_per_wave"] // 1024, launches_per_train=per_train,
+                quads_by_mapped_samples=[int((n == k).sum()) for k in range(5)],
+                a_regions_us=[t * 1e6 for t in ra], b_regions_us=[t * 1e6 for t in rb], a_us=med_a * 1e6, b_us=med_b * 1e6,
+                a_spread_us=spread * 1e6, b_spread_us=(max(rb) - min(rb)) * 1e6, b_over_a=med_b / med_a, target_met=bool(med_b <= med_a + spread))
+
+
+def main_ss2(args):
+    rows = []
+    what = "tinted" if args.tint else "plain"
+    for lens in args.lenses.split(","):
+        r = measure_ss2(lens, args.repeats, max(0.2, args.region), args.tint)
+        rows.append(r)
+        print(f"4K cube/{lens}, 2x2 supersampling, {what} [{r['block']} blocks, {r['lds_kib']} KiB staging; quads with 0..4 mapped samples: "
+              f"{r['quads_by_mapped_samples']}], {r['launches_per_train']} launches per train, {args.repeats} x A/B alternated:\n"
+              f"  A  16 full-size frames, {what:6s}   {r['a_us']:8.1f} us per launch (regions {fmt(r['a_regions_us'])}; spread {r['a_spread_us']:.1f})\n"
+              f"  B  16 half-size frames, ss2      {r['b_us']:8.1f} us per launch (regions {fmt(r['b_regions_us'])}; spread {r['b_spread_us']:.1f})\n"
+              f"  B == numpy average of A; B / A = {r['b_over_a']:.3f}; expectation B <= A + spread: {'met' if r['target_met'] else 'MISSED'}", flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def fmt(ts):
     return ", ".join("%.1f" % x for x in ts)
 
@@ -183,9 +266,12 @@ def main():
     ap.add_argument("--region", type=float, default=0.25, help="seconds per timed region (at least 0.2)")
     ap.add_argument("--out", default=None, help="also write the results as JSON lines to this file")
     ap.add_argument("--tint", action="store_true", help="f_rubix: 8-bit rubix launch A' / tinted truecolour B' / plain truecolour B")
+    ap.add_argument("--ss2", action="store_true", help="2x2 supersampling: full-size truecolour launch A (with --tint: the tinted one) / fused ss2 launch B")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_rgba.py measures on the GPU; there is none here")
+    if args.ss2:
+        return main_ss2(args)
     if args.tint:
         return main_tint(args)
     rows = []
