@@ -240,18 +240,27 @@ def test_batch_wraps_the_ring_of_truecolour_globes(bk):
 
 
 # ---- 4. blocks without staging ------------------------------------------------------------------------------------------------
+TINTS_0_TO_7_AND_255 = np.array([0, 1, 2, 3, 4, 5, 6, 7, 255], np.uint8)
+
+
+def scrambled_table(rng):
+    """517 x 301 random offsets, 7 % of them NULL, tints drawn from 0 .. 7 and 255 pixel by pixel -> W, H, ps, off, tints"""
+    W, H, ps = 517, 301, 301
+    n = W * H
+    off = rng.integers(0, 6 * ps * ps, n, dtype=np.uint32)
+    off[rng.random(n) < 0.07] = O.NULL
+    tints = TINTS_0_TO_7_AND_255[rng.integers(0, len(TINTS_0_TO_7_AND_255), n)]
+    return W, H, ps, off, tints
+
+
 @pytest.mark.parametrize("tinted", [False, True])
 def test_scrambled_tables_and_blocks_without_staging(bk, tinted):
     """the tables of test_apply_rgba_gpu.py's test of the same name: (a) every block staged, (b) the staging buffer forced so small
     that every list exceeds it, (c) blocks that have no chunk list at all; tints drawn from 0 .. 7 and 255 pixel by pixel"""
     rng = np.random.default_rng(77)
-    values = np.array([0, 1, 2, 3, 4, 5, 6, 7, 255], np.uint8)
+    values = TINTS_0_TO_7_AND_255
     lut = random_luts(4) if tinted else None
-    W, H, ps = 517, 301, 301
-    n = W * H
-    off = rng.integers(0, 6 * ps * ps, n, dtype=np.uint32)
-    off[rng.random(n) < 0.07] = O.NULL
-    tints = values[rng.integers(0, len(values), n)]
+    W, H, ps, off, tints = scrambled_table(rng)
     planes = planes_of(ps, 0, seed=11)
     Wo, Ho = (W + 1) // 2, (H + 1) // 2
     ctx = make_ctx(bk, W, H, 4)
@@ -288,6 +297,44 @@ def test_scrambled_tables_and_blocks_without_staging(bk, tinted):
     st = ctx.tile_stats()
     assert st["slow"] > 0, st
     np.testing.assert_array_equal(got, paste(bg, quad_means(off, tints, W, H, planes, lut), 0, 0), err_msg=str(st))
+    ctx.close()
+
+
+@pytest.mark.parametrize("tinted", [False, True])
+def test_blocks_without_staging_in_a_batch(bk, tinted):
+    """the frame loop of the direct gather: table (a) above under 128 x 8 blocks and 1 KiB of staging - every list exceeds it - launched
+    for FIVE frames from globe 1 of a ring of two truecolour globes, so that a block visit serves several frames of alternating globes
+    (test 4 launches such blocks for one frame, test 3's batch is fully staged).  Every frame and the bytes between the frames are
+    compared: a visit that read its first frame's globe for all its frames fails here."""
+    import torch
+    W, H, ps, off, tints = scrambled_table(np.random.default_rng(77))
+    lut = random_luts(4) if tinted else None
+    G, F, globe0 = 2, 5, 1
+    Wo, Ho = (W + 1) // 2, (H + 1) // 2
+    ctx = make_ctx(bk, W, H, 4 * G)
+    planes = [planes_of(ps, g, seed=11) for g in range(G)]
+    for g in range(G):
+        upload_planes(ctx, g, planes[g])
+    ctx.set_lensmap(off, tints)
+    ctx.set_tile_shape(1)
+    ctx.set_tile_shape(401)
+    pitch = 4 * (Wo + 3)
+    bg = background(Ho + 4, pitch)
+    want = [paste(bg, quad_means(off, tints, W, H, planes[g], lut), 2, 1) for g in range(G)]
+    assert not np.array_equal(want[0], want[1])
+    stride = bg.size + 3 * pitch + 4                       # frames apart by rows nobody owns and 4 bytes more
+    filled = np.full(F * stride, 9, np.uint8)
+    for f in range(F):
+        filled[f * stride:f * stride + bg.size] = bg.ravel()
+    out = torch.from_numpy(filled).cuda()
+    ctx.apply_rgba_ss2_device(out.data_ptr(), pitch, stride, globe0=globe0, nframes=F, x0=2, y0=1, lut=lut)
+    torch.cuda.synchronize()
+    st = ctx.tile_stats()
+    assert st["slow"] > 0, st
+    got = out.cpu().numpy()
+    for f in range(F):
+        np.testing.assert_array_equal(got[f * stride:f * stride + bg.size].reshape(bg.shape), want[(globe0 + f) % G], err_msg=f"frame {f} {st}")
+        assert (got[f * stride + bg.size:(f + 1) * stride] == 9).all(), f"bytes behind frame {f} were written"
     ctx.close()
 
 
