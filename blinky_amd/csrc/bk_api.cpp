@@ -139,6 +139,7 @@ static void free_maps(bk_ctx *ctx)
     ctx->lensmap_valid = false;
     ctx->spans_valid = false;
     bk::coopmap_invalidate(ctx);
+    bk::footprint_invalidate(ctx);
 }
 
 extern "C" void bk_destroy(bk_ctx *ctx)
@@ -153,6 +154,7 @@ extern "C" void bk_destroy(bk_ctx *ctx)
     hipFree(ctx->d_globe);
     hipFree(ctx->d_plate_stage);
     hipFree(ctx->d_rgba_stage);
+    bk::footprint_free(ctx);
     hipFree(ctx->d_pal);
     hipFree(ctx->d_lut_rgba);
     hipFree(ctx->d_display);
@@ -231,6 +233,7 @@ void bk::empty_context(bk_ctx *ctx)
     (void)hipFree(ctx->d_globe); ctx->d_globe = nullptr; ctx->globe_bytes = 0;
     (void)hipFree(ctx->d_plate_stage); ctx->d_plate_stage = nullptr;
     (void)hipFree(ctx->d_rgba_stage); ctx->d_rgba_stage = nullptr; ctx->rgba_stage_bytes = 0;
+    bk::footprint_free(ctx);
     ctx->W = ctx->H = ctx->ps = ctx->gp = ctx->ph = 0;
     ctx->row0 = ctx->row1 = 0;
     ctx->lensmap_valid = false;
@@ -267,6 +270,7 @@ extern "C" int bk_resize(bk_ctx *ctx, int width, int height)
     ctx->W = width; ctx->H = height; ctx->ps = ps; ctx->gp = gp; ctx->ph = ph;
     ctx->row0 = 0; ctx->row1 = height;
     ctx->lensmap_valid = false;
+    bk::footprint_invalidate(ctx);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail_empty(ctx->fail(BK_E_HIP, "bk_resize: hipStreamSynchronize failed"));
     (void)hipFree(ctx->d_plate_stage);
     ctx->d_plate_stage = nullptr;
@@ -294,6 +298,7 @@ extern "C" int bk_set_rows(bk_ctx *ctx, int row0, int row1)
     ctx->row0 = row0; ctx->row1 = row1;
     ctx->lensmap_valid = false;
     ctx->spans_valid = false;
+    bk::footprint_invalidate(ctx);
     return alloc_maps(ctx);
 }
 
@@ -443,6 +448,7 @@ extern "C" int bk_set_lensmap(bk_ctx *ctx, const uint32_t *offsets, const uint8_
     ctx->lensmap_valid = true;
     ctx->spans_valid = false;
     bk::coopmap_invalidate(ctx);
+    bk::footprint_invalidate(ctx);
     return BK_OK;
 }
 
@@ -587,13 +593,10 @@ extern "C" int bk_upload_plate_rgba_device(bk_ctx *ctx, int globe, int plate, co
     return bk::launch_plate_rgba_retile(ctx, plane0, (const uint8_t *)src_dev, (size_t)src_pitch);
 }
 
-extern "C" int bk_upload_plate_rgba(bk_ctx *ctx, int globe, int plate, const uint8_t *src, int src_pitch)
+// d_rgba_stage: [ps][4 * ps], where a truecolour plate from the host lands before it is de-interleaved
+static int ensure_rgba_stage(bk_ctx *ctx, const char *who)
 {
-    if (!ctx || !src) return BK_E_INVALID;
-    if (int r = rgba_plate_args(ctx, "bk_upload_plate_rgba", globe, plate, src_pitch)) return r;
-    if (int r = ensure_device(ctx)) return r;
-    bk::Range range("bk_upload_plate_rgba");
-    const size_t ps = ctx->ps, row = 4 * ps, bytes = row * ps;
+    const size_t bytes = (size_t)4 * ctx->ps * ctx->ps;
     if (ctx->rgba_stage_bytes != bytes) {                    // (first use, or the platesize has changed since)
         BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         (void)hipFree(ctx->d_rgba_stage);
@@ -601,13 +604,86 @@ extern "C" int bk_upload_plate_rgba(bk_ctx *ctx, int globe, int plate, const uin
         ctx->rgba_stage_bytes = 0;
         if (hipMalloc((void **)&ctx->d_rgba_stage, bytes) != hipSuccess) {
             (void)hipGetLastError();
-            return ctx->fail(BK_E_NOMEM, "bk_upload_plate_rgba: out of device memory (plate staging, %zu bytes)", bytes);
+            return ctx->fail(BK_E_NOMEM, "%s: out of device memory (plate staging, %zu bytes)", who, bytes);
         }
         ctx->rgba_stage_bytes = bytes;
     }
+    return BK_OK;
+}
+
+extern "C" int bk_upload_plate_rgba(bk_ctx *ctx, int globe, int plate, const uint8_t *src, int src_pitch)
+{
+    if (!ctx || !src) return BK_E_INVALID;
+    if (int r = rgba_plate_args(ctx, "bk_upload_plate_rgba", globe, plate, src_pitch)) return r;
+    if (int r = ensure_device(ctx)) return r;
+    bk::Range range("bk_upload_plate_rgba");
+    const size_t ps = ctx->ps, row = 4 * ps;
+    if (int r = ensure_rgba_stage(ctx, "bk_upload_plate_rgba")) return r;
     BK_HIP(ctx, hipMemcpy2DAsync(ctx->d_rgba_stage, row, src, (size_t)src_pitch, row, ps, hipMemcpyHostToDevice, ctx->stream));
     uint8_t *plane0 = ctx->d_globe + (size_t)(4 * globe) * ctx->globe_stride() + (size_t)plate * ctx->plate_bytes();
     if (int r = bk::launch_plate_rgba_retile(ctx, plane0, ctx->d_rgba_stage, row)) return r;
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BK_OK;
+}
+
+// ---- the lensmap's footprint: which 16x8-texel tiles of each plate the owned rows read (no counterpart in the reference beyond
+// globe.plates[i].display, fisheye.c:1976) ---------------------------------------------------------------------------------------
+static int footprint_ready(bk_ctx *ctx, const char *who)
+{
+    if (!ctx->lensmap_valid || !ctx->d_offsets) return ctx->fail(BK_E_STATE, "%s: no lensmap", who);
+    if (ctx->footprint_valid) return BK_OK;
+    if (int r = ensure_device(ctx)) return r;
+    return bk::launch_footprint(ctx);
+}
+
+extern "C" int bk_plate_footprint(bk_ctx *ctx, int plate, int rect[4], int *ntiles, uint8_t *tiles)
+{
+    if (!ctx || !rect) return BK_E_INVALID;
+    if (ctx->device < 0) return ctx->fail(BK_E_STATE, "bk_plate_footprint: this context was created without a device (BK_DEVICE_NONE)");
+    if (plate < 0 || plate >= BK_MAX_PLATES) return ctx->fail(BK_E_INVALID, "bk_plate_footprint: bad plate %d", plate);
+    if (int r = footprint_ready(ctx, "bk_plate_footprint")) return r;
+    const int *s = ctx->fp_summary(plate);
+    rect[0] = 16 * s[1];
+    rect[1] = 8 * s[2];
+    rect[2] = std::min(16 * s[3], ctx->ps);
+    rect[3] = std::min(8 * s[4], ctx->ps);
+    if (ntiles) *ntiles = s[0];
+    if (tiles) {
+        const size_t tpp = ctx->plate_tiles(), t0 = (size_t)plate * tpp;
+        for (size_t t = 0; t < tpp; ++t) tiles[t] = (uint8_t)((ctx->h_fp[(t0 + t) >> 5] >> ((t0 + t) & 31)) & 1u);
+    }
+    return BK_OK;
+}
+
+extern "C" int bk_upload_plate_rgba_footprint_device(bk_ctx *ctx, int globe, int plate, const void *src_dev, int src_pitch)
+{
+    if (!ctx || !src_dev) return BK_E_INVALID;
+    if (int r = rgba_plate_args(ctx, "bk_upload_plate_rgba_footprint_device", globe, plate, src_pitch)) return r;
+    if (int r = ensure_device(ctx)) return r;
+    if (int r = footprint_ready(ctx, "bk_upload_plate_rgba_footprint_device")) return r;
+    if (ctx->fp_summary(plate)[0] == 0) return BK_OK;        // nothing of this plate is read: no launch
+    bk::Range range("bk_upload_plate_rgba_footprint_device");
+    uint8_t *plane0 = ctx->d_globe + (size_t)(4 * globe) * ctx->globe_stride() + (size_t)plate * ctx->plate_bytes();
+    return bk::launch_plate_rgba_retile_footprint(ctx, plate, plane0, (const uint8_t *)src_dev, (size_t)src_pitch);
+}
+
+extern "C" int bk_upload_plate_rgba_footprint(bk_ctx *ctx, int globe, int plate, const uint8_t *src, int src_pitch)
+{
+    if (!ctx || !src) return BK_E_INVALID;
+    if (int r = rgba_plate_args(ctx, "bk_upload_plate_rgba_footprint", globe, plate, src_pitch)) return r;
+    if (int r = ensure_device(ctx)) return r;
+    if (int r = footprint_ready(ctx, "bk_upload_plate_rgba_footprint")) return r;
+    const int *s = ctx->fp_summary(plate);
+    if (s[0] == 0) return BK_OK;
+    bk::Range range("bk_upload_plate_rgba_footprint");
+    if (int r = ensure_rgba_stage(ctx, "bk_upload_plate_rgba_footprint")) return r;
+    // the rect only, to the same coordinates of the staging plate: what lies outside it is neither copied nor read by the kernel
+    const size_t ps = ctx->ps, row = 4 * ps, x0 = 16 * (size_t)s[1], y0 = 8 * (size_t)s[2];
+    const size_t x1 = std::min<size_t>(16 * (size_t)s[3], ps), y1 = std::min<size_t>(8 * (size_t)s[4], ps);
+    BK_HIP(ctx, hipMemcpy2DAsync(ctx->d_rgba_stage + y0 * row + 4 * x0, row, src + y0 * (size_t)src_pitch + 4 * x0, (size_t)src_pitch, 4 * (x1 - x0), y1 - y0,
+                                 hipMemcpyHostToDevice, ctx->stream));
+    uint8_t *plane0 = ctx->d_globe + (size_t)(4 * globe) * ctx->globe_stride() + (size_t)plate * ctx->plate_bytes();
+    if (int r = bk::launch_plate_rgba_retile_footprint(ctx, plate, plane0, ctx->d_rgba_stage, row)) return r;
     BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return BK_OK;
 }

@@ -181,14 +181,10 @@ __global__ __launch_bounds__(256) void plate_retile_kernel(uint8_t *__restrict__
 // globe slots (plane_stride bytes apart): byte c of every texel goes to slot c, in the tiled layout every slot has.  A thread reads the
 // 64 contiguous bytes of 16 texels of a row and writes one 16-byte chunk into each plane (the texels past ps of a row's last chunk as
 // zeros: padding nothing reads).  wide: src and src_pitch are multiples of 16 (vector loads); else multiples of 4 (dword loads) or
-// of nothing (align1: byte loads).
-__global__ __launch_bounds__(256) void plate_rgba_retile_kernel(uint8_t *__restrict__ plane0, size_t plane_stride, const uint8_t *__restrict__ src,
-                                                                size_t src_pitch, int ps, int gp, int ph, int wide, int align1)
+// of nothing (align1: byte loads).  rgba_retile_chunk is that thread's work for chunk cx of row py; both re-tiling kernels below call it.
+static __device__ __forceinline__ void rgba_retile_chunk(uint8_t *__restrict__ plane0, size_t plane_stride, const uint8_t *__restrict__ src,
+                                                         size_t src_pitch, int ps, int gp, int ph, int py, int cx, int wide, int align1)
 {
-    const int cpr = (ps + 15) >> 4;
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= cpr * ps) return;
-    const int py = id / cpr, cx = id - py * cpr;
     const int cnt = min(16, ps - cx * 16);                  // texels of this chunk inside the plate
     const uint8_t *s = src + (size_t)py * src_pitch + (size_t)cx * 64;
     uint32_t t[16];                                          // the 16 texels
@@ -216,6 +212,74 @@ __global__ __launch_bounds__(256) void plate_rgba_retile_kernel(uint8_t *__restr
                    (((t[4 * j + 3] >> (8 * c)) & 0xFFu) << 24);
         *reinterpret_cast<uint4 *>(out + (size_t)c * plane_stride) = make_uint4(w[0], w[1], w[2], w[3]);
     }
+}
+
+__global__ __launch_bounds__(256) void plate_rgba_retile_kernel(uint8_t *__restrict__ plane0, size_t plane_stride, const uint8_t *__restrict__ src,
+                                                                size_t src_pitch, int ps, int gp, int ph, int wide, int align1)
+{
+    const int cpr = (ps + 15) >> 4;
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= cpr * ps) return;
+    const int py = id / cpr, cx = id - py * cpr;
+    rgba_retile_chunk(plane0, plane_stride, src, src_pitch, ps, gp, ph, py, cx, wide, align1);
+}
+
+// ---------------------------------------------------------------------------------------
+// the lensmap's FOOTPRINT: which 16x8-texel tiles (128-byte lines) of a globe slot the owned rows read.  No counterpart in the
+// reference beyond globe.plates[i].display (fisheye.c:1976), the same question asked per plate.
+// ---------------------------------------------------------------------------------------
+// one thread per lensmap entry: bit (device offset >> 7) of `bits`.  Neighbouring pixels read the same tile, so the bit is tested first
+// and almost no thread gets as far as the atomic (as truncate_scan_kernel does for display)
+__global__ __launch_bounds__(256) void footprint_mark_kernel(const uint32_t *__restrict__ off, size_t n, uint32_t ntiles, uint32_t *__restrict__ bits)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t o = off[i];
+    if (o == BK_NULL_OFFSET) return;
+    const uint32_t t = o >> 7;
+    if (t >= ntiles) return;                                 // (never outside the bitmap, whatever the table holds)
+    const uint32_t m = 1u << (t & 31u);
+    if ((__hip_atomic_load(&bits[t >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m) == 0) atomicOr(&bits[t >> 5], m);
+}
+
+// one workgroup per plate: summary[5 * plate ..] = tiles read, then x0, y0, x1, y1 of their bounding box in tiles (half-open; 0 0 0 0 when
+// none).  tpr x tile_rows tiles per plate.
+__global__ __launch_bounds__(256) void footprint_reduce_kernel(const uint32_t *__restrict__ bits, int tpr, int tile_rows, int *__restrict__ summary)
+{
+    __shared__ int s[5];
+    const int plate = blockIdx.x, tpp = tpr * tile_rows;
+    if (threadIdx.x < 5) s[threadIdx.x] = threadIdx.x == 1 || threadIdx.x == 2 ? 0x7FFFFFFF : 0;
+    __syncthreads();
+    int cnt = 0, x0 = 0x7FFFFFFF, y0 = 0x7FFFFFFF, x1 = 0, y1 = 0;
+    for (int t = threadIdx.x; t < tpp; t += 256) {
+        const uint32_t g = (uint32_t)(plate * tpp + t);
+        if ((bits[g >> 5] >> (g & 31u)) & 1u) {
+            const int ty = t / tpr, tx = t - ty * tpr;
+            ++cnt;
+            x0 = min(x0, tx); y0 = min(y0, ty); x1 = max(x1, tx + 1); y1 = max(y1, ty + 1);
+        }
+    }
+    if (cnt) { atomicAdd(&s[0], cnt); atomicMin(&s[1], x0); atomicMin(&s[2], y0); atomicMax(&s[3], x1); atomicMax(&s[4], y1); }
+    __syncthreads();
+    if (threadIdx.x < 5) summary[5 * plate + threadIdx.x] = s[0] ? s[threadIdx.x] : 0;
+}
+
+// plate_rgba_retile_kernel for the tiles of the footprint only.  The grid covers the chunks of the plate's bounding box (bw tiles wide,
+// from tile (bx0, by0)); a thread tests its tile's bit (tile0 = the plate's first tile in `bits`) and leaves if it is clear.  The eight
+// chunks of a tile are eight neighbouring lanes and the tiles of a tile row follow each other, so a wave's store into a plane is eight
+// whole 128-byte lines - 1 KiB in one piece where the box is at least eight tiles wide - never a line shared with another wave.
+__global__ __launch_bounds__(256) void plate_rgba_retile_footprint_kernel(uint8_t *__restrict__ plane0, size_t plane_stride, const uint8_t *__restrict__ src,
+                                                                          size_t src_pitch, int ps, int gp, int ph, int wide, int align1,
+                                                                          const uint32_t *__restrict__ bits, uint32_t tile0, int bx0, int by0, int bw, int nchunks)
+{
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= nchunks) return;
+    const int tb = id >> 3, by = tb / bw;
+    const int ty = by0 + by, tx = bx0 + tb - by * bw, py = ty * 8 + (id & 7);
+    const uint32_t t = tile0 + (uint32_t)(ty * (gp >> 4) + tx);
+    if (((bits[t >> 5] >> (t & 31u)) & 1u) == 0) return;
+    if (py >= ps || tx * 16 >= ps) return;                   // rows of the last tile row past the plate; (padding tiles are never marked)
+    rgba_retile_chunk(plane0, plane_stride, src, src_pitch, ps, gp, ph, py, tx, wide, align1);
 }
 
 // sparse patches of a device table (the handful of lensmap entries / texel corners the host re-derives on the
@@ -342,6 +406,53 @@ int launch_plate_rgba_retile(bk_ctx *ctx, uint8_t *plane0, const uint8_t *src_de
     const uintptr_t a = reinterpret_cast<uintptr_t>(src_dev) | (uintptr_t)src_pitch;
     hipLaunchKernelGGL(plate_rgba_retile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, plane0, ctx->globe_stride(),
                        src_dev, src_pitch, ctx->ps, ctx->gp, ctx->ph, (a & 15) == 0 ? 1 : 0, (a & 3) != 0 ? 1 : 0);
+    BK_HIP(ctx, hipGetLastError());
+    return BK_OK;
+}
+
+void footprint_free(bk_ctx *ctx)
+{
+    (void)hipFree(ctx->d_fp_bits);
+    if (ctx->h_fp) (void)hipHostFree(ctx->h_fp);
+    ctx->d_fp_bits = nullptr;
+    ctx->h_fp = nullptr;
+    ctx->fp_words = 0;
+    ctx->footprint_valid = false;
+}
+
+int launch_footprint(bk_ctx *ctx)
+{
+    if (ctx->footprint_valid) return BK_OK;
+    const size_t tiles = BK_MAX_PLATES * ctx->plate_tiles(), words = (tiles + 31) / 32, all = words + 5 * BK_MAX_PLATES;   // bitmap, then the summary
+    if (ctx->fp_words != words || !ctx->d_fp_bits || !ctx->h_fp) {            // (first use, or the platesize has changed since)
+        BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        footprint_free(ctx);
+        BK_HIP(ctx, hipMalloc((void **)&ctx->d_fp_bits, all * sizeof(uint32_t)));
+        BK_HIP(ctx, hipHostMalloc((void **)&ctx->h_fp, all * sizeof(uint32_t), hipHostMallocDefault));
+        ctx->fp_words = words;
+    }
+    const size_t n = (size_t)ctx->W * ctx->rows();
+    BK_HIP(ctx, hipMemsetAsync(ctx->d_fp_bits, 0, words * sizeof(uint32_t), ctx->stream));
+    if (n) hipLaunchKernelGGL(footprint_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_offsets, n, (uint32_t)tiles,
+                              ctx->d_fp_bits);
+    hipLaunchKernelGGL(footprint_reduce_kernel, dim3(BK_MAX_PLATES), dim3(256), 0, ctx->stream, ctx->d_fp_bits, ctx->gp >> 4, ctx->ph >> 3,
+                       reinterpret_cast<int *>(ctx->d_fp_bits + words));
+    BK_HIP(ctx, hipGetLastError());
+    BK_HIP(ctx, hipMemcpyAsync(ctx->h_fp, ctx->d_fp_bits, all * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->footprint_valid = true;
+    return BK_OK;
+}
+
+int launch_plate_rgba_retile_footprint(bk_ctx *ctx, int plate, uint8_t *plane0, const uint8_t *src_dev, size_t src_pitch)
+{
+    const int *box = ctx->fp_summary(plate) + 1;             // x0, y0, x1, y1 in tiles
+    const int bw = box[2] - box[0], nchunks = bw * (box[3] - box[1]) * 8;
+    if (nchunks <= 0) return BK_OK;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src_dev) | (uintptr_t)src_pitch;
+    hipLaunchKernelGGL(plate_rgba_retile_footprint_kernel, dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, ctx->stream, plane0, ctx->globe_stride(),
+                       src_dev, src_pitch, ctx->ps, ctx->gp, ctx->ph, (a & 15) == 0 ? 1 : 0, (a & 3) != 0 ? 1 : 0, ctx->d_fp_bits,
+                       (uint32_t)((size_t)plate * ctx->plate_tiles()), box[0], box[1], bw, nchunks);
     BK_HIP(ctx, hipGetLastError());
     return BK_OK;
 }

@@ -74,6 +74,14 @@ struct bk_ctx {
     uint8_t *d_plate_stage = nullptr;  // [ps][gp] row-major staging of one plate for bk_upload_plate / bk_download_plate
     uint8_t *d_rgba_stage = nullptr;   // [ps][4*ps] one truecolour plate on its way from the host (bk_upload_plate_rgba); allocated on first use
     size_t rgba_stage_bytes = 0;
+    // the footprint of the lensmap (bk_plate_footprint, bk_upload_plate_rgba_footprint*): bit t of d_fp_bits = "some entry of the owned rows
+    // reads 128-byte tile t of a globe slot" (t = device offset >> 7, plates back to back); computed on the first query after the lensmap
+    // changed (launch_footprint), never by a build.  h_fp (pinned) = the same bits, then 5 ints per plate: tiles read, x0, y0, x1, y1 of
+    // their bounding box in tiles (half-open; all 0 when nothing is read)
+    uint32_t *d_fp_bits = nullptr;
+    uint32_t *h_fp = nullptr;
+    size_t fp_words = 0;               // uint32 words of the bitmap the two buffers were allocated for
+    bool footprint_valid = false;
     // bk_upload_plate_async: pinned host buffers the caller's rows are copied into, their device-side staging twins and
     // the event that says "this slot's DMA + retile are done" - three slots, so that the DMA of plate k overlaps the
     // engine's render of plate k+1
@@ -184,6 +192,8 @@ struct bk_ctx {
     int rows() const { return row1 - row0; }
     size_t plate_bytes() const { return (size_t)gp * ph; }
     size_t globe_stride() const { return (size_t)BK_MAX_PLATES * gp * ph; }
+    size_t plate_tiles() const { return (size_t)(gp >> 4) * (ph >> 3); }      // 16x8-texel tiles (128-byte lines) of a plate, padding included
+    const int *fp_summary(int plate) const { return reinterpret_cast<const int *>(h_fp + fp_words) + 5 * plate; }   // valid while footprint_valid
 };
 
 #define BK_HIP(ctx, expr)                                                               \
@@ -205,6 +215,12 @@ int launch_plate_retile(bk_ctx *ctx, uint8_t *plate_tiled, int to_tiled, uint8_t
 // a row-major plate of 32-bit texels (device memory, rows src_pitch bytes apart) -> the same plate of four consecutive globe slots,
 // byte c of every texel into slot c's tiles; plane0 = the plate in the first of the four slots
 int launch_plate_rgba_retile(bk_ctx *ctx, uint8_t *plane0, const uint8_t *src_dev, size_t src_pitch);
+// the lensmap's footprint (bk_ctx::d_fp_bits / h_fp) if it is not the current one: mark, reduce, ONE host synchronisation
+int launch_footprint(bk_ctx *ctx);
+inline void footprint_invalidate(bk_ctx *ctx) { ctx->footprint_valid = false; }      // wherever the lensmap or the owned rows change
+void footprint_free(bk_ctx *ctx);
+// launch_plate_rgba_retile for the tiles of `plate` in the footprint only (which must be current and not empty for that plate)
+int launch_plate_rgba_retile_footprint(bk_ctx *ctx, int plate, uint8_t *plane0, const uint8_t *src_dev, size_t src_pitch);
 int launch_scatter32(bk_ctx *ctx, uint32_t *dst, const uint32_t *h_idx, const uint32_t *h_val, size_t n);   // dst[idx[i]] = val[i]; synchronous
 int launch_scatter8(bk_ctx *ctx, uint8_t *dst, const uint32_t *h_idx, const uint8_t *h_val, size_t n);
 // the owned rows of the lensmap as the reference leaves them when its scan stops at the pixel with scan key bad_key - 1 (everything it

@@ -2201,6 +2201,7 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
     ctx->last_bad_key = 0;
     ctx->spans_valid = false;
     bk::coopmap_invalidate(ctx);
+    bk::footprint_invalidate(ctx);                    // (here, in front of every way out: whatever the build leaves in the table is new)
     for (int i = 0; i < BK_MAX_PLATES; ++i) { ctx->display[i] = 0; if (display_out) display_out[i] = 0; }
     ctx->last_build_ms = 0;
     ctx->last_host_eval_ms = ctx->last_kernel_wall_ms = 0;
@@ -2462,6 +2463,7 @@ extern "C" int bk_truncate_build(bk_ctx *ctx, unsigned int bad_key, int display_
     ctx->last_bad_key = bad_key;
     ctx->spans_valid = false;
     bk::coopmap_invalidate(ctx);
+    bk::footprint_invalidate(ctx);
     for (int i = 0; i < BK_MAX_PLATES; ++i) { ctx->display[i] = i < ctx->numplates ? disp[i] : 0; if (display_out) display_out[i] = ctx->display[i]; }
     return BK_OK;
 }

@@ -75,6 +75,9 @@ _SIGS = {
     "bk_upload_plate_async": (_i, [_vp, _i, _i, _vp, _i]),
     "bk_upload_plate_rgba": (_i, [_vp, _i, _i, _vp, _i]),
     "bk_upload_plate_rgba_device": (_i, [_vp, _i, _i, _vp, _i]),
+    "bk_plate_footprint": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "bk_upload_plate_rgba_footprint": (_i, [_vp, _i, _i, _vp, _i]),
+    "bk_upload_plate_rgba_footprint_device": (_i, [_vp, _i, _i, _vp, _i]),
     "bk_apply_rgba_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i]),
     "bk_apply_rgba_tinted_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
     "bk_apply_rgba_ss2_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
@@ -398,6 +401,25 @@ class Context:
 
     def upload_plate_rgba_device(self, globe, plate, ptr, pitch):
         self._chk(lib.bk_upload_plate_rgba_device(self._h, globe, plate, ptr, pitch))
+
+    # the lensmap's footprint: the 16x8-texel tiles of a plate the owned rows read
+    def plate_footprint(self, plate, tiles=False):
+        """((x0, y0, x1, y1) in texels - half-open, tile-granular, all 0 when nothing is read -, tiles read[, uint8 [globe_rows() / 8]
+        [globe_pitch() / 16], 1 = read])"""
+        rect, n = (_i * 4)(), _i()
+        mask = np.zeros((self.globe_rows() // 8, self.globe_pitch() // 16), np.uint8) if tiles else None
+        self._chk(lib.bk_plate_footprint(self._h, plate, rect, C.byref(n), _ptr(mask)))
+        return (tuple(rect), n.value, mask) if tiles else (tuple(rect), n.value)
+
+    def upload_plate_rgba_footprint(self, globe, plate, src, pitch=None):
+        """upload_plate_rgba writing the footprint's tiles only; src outside plate_footprint's rect is never read"""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if pitch is None:
+            pitch = src.shape[-1] * (src.shape[-2] if src.ndim == 3 else 1)
+        self._chk(lib.bk_upload_plate_rgba_footprint(self._h, globe, plate, _ptr(src), pitch))
+
+    def upload_plate_rgba_footprint_device(self, globe, plate, ptr, pitch):
+        self._chk(lib.bk_upload_plate_rgba_footprint_device(self._h, globe, plate, ptr, pitch))
 
     def globe_device_ptr(self, frame=0):
         return lib.bk_globe_device_ptr(self._h, frame)

@@ -21,7 +21,8 @@
  *   - there is no CPU fallback: without a usable GPU bk_create fails.
  *   - texels and pixels are 8-bit palettised, as the reference's (TyrQuake's software rasteriser).  TRUECOLOUR - 32-bit plates
  *     warped into 32-bit frames, for hosts whose plates are frame buffers of a present-day renderer - is bk_upload_plate_rgba /
- *     bk_upload_plate_rgba_device / bk_apply_rgba_device / bk_apply_rgba_tinted_device / bk_apply_rgba_ss2_device: a 32-bit globe is four byte planes in four consecutive slots of the same
+ *     bk_upload_plate_rgba_device / bk_plate_footprint / bk_upload_plate_rgba_footprint / bk_upload_plate_rgba_footprint_device /
+ *     bk_apply_rgba_device / bk_apply_rgba_tinted_device / bk_apply_rgba_ss2_device: a 32-bit globe is four byte planes in four consecutive slots of the same
  *     globe ring, so lens build, lensmap and everything else in this header are shared with the 8-bit path as they are.
  */
 #ifndef BLINKY_HIP_H
@@ -224,6 +225,29 @@ int   bk_fill_plate_lcg(bk_ctx *ctx, int frame, int plate, uint32_t seed_frame);
  * Both end a resident session first, as every device entry point but the 8-bit plate uploads. */
 int   bk_upload_plate_rgba(bk_ctx *ctx, int globe, int plate, const uint8_t *src_host, int src_pitch_bytes);
 int   bk_upload_plate_rgba_device(bk_ctx *ctx, int globe, int plate, const void *src_dev, int src_pitch_bytes);
+/* The lensmap's FOOTPRINT (no counterpart in the reference beyond `display`: globe.plates[i].display, fisheye.c:1976, exists so that
+ * plates the lens never looks at are not rendered - this is the same question asked per 16x8-texel tile, one 128-byte line of a slot).
+ * bk_plate_footprint: which part of plate `plate` the current lensmap (owned rows, bk_set_rows) reads.  rect = {x0, y0, x1, y1} in
+ * texels, half-open, tile-granular (x0 / x1 multiples of 16, y0 / y1 of 8, x1 and y1 clipped to ps): the bounding box of the tiles read;
+ * all 0 when nothing is read.  *ntiles (nullable) = tiles read.  tiles (nullable): [bk_globe_rows()/8][bk_globe_pitch()/16] bytes,
+ * 1 = read; padding tiles (past ps) are never 1.  ntiles > 0 exactly when bk_build's display flag is set for these rows.  Tints play
+ * no part.  Computed on the device on the first query (or footprint upload) after the lensmap or the owned rows changed - one pass over
+ * the lensmap, one host synchronisation - and kept until they change again: bk_build, bk_set_lensmap, bk_truncate_build, bk_resize,
+ * bk_set_rows (a bk_build that returns BK_PENDING changes nothing).  bk_build itself never computes it.  BK_E_STATE without a lensmap.
+ * A renderer scissors or culls with rect; a stripe context gets the footprint of its own rows.
+ * bk_upload_plate_rgba_footprint / _device: bk_upload_plate_rgba / bk_upload_plate_rgba_device in arguments, ordering, alignment
+ * classes (16 / 4 / 1-byte src and pitch), errors and the resident session they end - but ONLY the tiles of the footprint are written
+ * (whole tiles, into all four byte planes); every other byte of the four slots keeps its value.  SOURCE TEXELS OUTSIDE rect ARE NEVER
+ * READ - neither by the kernel nor, in the host form, by the copy (only rect travels, through the same staging buffer) - so a renderer
+ * that scissored to rect may leave the rest of src unwritten.  A plate with an empty footprint is BK_OK and launches nothing.
+ * BK_E_STATE without a lensmap.
+ * THE CONTRACT: a globe uploaded through the footprint is complete for the lensmap (and owned rows) it was uploaded under, and for
+ * nothing else.  After a lensmap change upload again before the next apply - a live renderer uploads every frame anyway.
+ * bk_download_plate shows stale tiles outside the footprint.  Every bk_apply* reads such a globe exactly as it reads a fully
+ * uploaded one (measured: profiles/rgba_footprint_upload.txt). */
+int   bk_plate_footprint(bk_ctx *ctx, int plate, int rect[4], int *ntiles, uint8_t *tiles);
+int   bk_upload_plate_rgba_footprint_device(bk_ctx *ctx, int globe, int plate, const void *src_dev, int src_pitch_bytes);
+int   bk_upload_plate_rgba_footprint(bk_ctx *ctx, int globe, int plate, const uint8_t *src_host, int src_pitch_bytes);
 
 /* ---- lensmap apply ------------------------------------------------------------------
  * replaces: render_lensmap (fisheye.c:2406-2424).  Unmapped pixels leave dst untouched.

@@ -7,7 +7,7 @@ At 3840x2160 cube/panini and cube/hammer, over the 64-slot LCG ring of the bench
 B's output is compared with A's plane by plane before anything is timed.  Timing: HIP events on the context's stream, warm-up
 launches first, regions of at least --region seconds made of ten event-timed trains of launches (a region's figure is the median
 train), A / B / A / B ... alternated --repeats times inside this one process.  The target: B's median <= A's median + A's own spread
-(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2]
+(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2] [--upload]
 
 --tint: the same protocol for f_rubix on truecolour frames, three launches alternated A' / B' / B:
   A'  one bk_apply_device launch of 64 8-bit frames with rubix_on = 1 (existing code: the same bytes through the same number of LUT
@@ -20,7 +20,17 @@ B' must equal A' plane by plane before anything is timed.  The target: B''s medi
   A  one bk_apply_rgba_device (--tint: bk_apply_rgba_tinted_device) launch of 16 full-size truecolour frames
   B  one bk_apply_rgba_ss2_device launch over the same globes (--tint: through the same tables) into 16 half-size frames
 B must equal the numpy average of A's full-size output (mapped samples only, (sum + n // 2) // n) before anything is timed.  B reads
-what A reads and stores a quarter of its bytes; the expectation: B's median <= A's median + A's own spread."""
+what A reads and stores a quarter of its bytes; the expectation: B's median <= A's median + A's own spread.
+
+--upload [--reps 31]: the per-frame loop of a live renderer, one truecolour globe per frame from device plates (16-byte aligned):
+  A  bk_upload_plate_rgba_device of every displayed plate
+  B  bk_upload_plate_rgba_footprint_device of the same plates (only the tiles the lensmap reads)
+  P  the one-frame bk_apply_rgba_device behind either; A + P and B + P are the frame
+The frame after B must equal the frame after A byte for byte before anything is timed.  Frames rotate through 16 truecolour globes and 4
+sets of source plates (out of the Infinity Cache by the time their turn comes again), A and B alternate frame by frame, --repeats blocks of
+--reps frames each way; a figure is the median of the block medians, its spread their max - min.  Printed with the footprint's tile
+count and the byte model (8 bytes per texel of every chunk / tile written).  The expectations: cube/hammer (footprint = everything)
+B <= A + A's spread; cube/panini B / A reported next to the tile ratio."""
 import argparse
 import json
 import os
@@ -220,6 +230,112 @@ def measure_ss2(lens, repeats, region_s, tint):
                 a_spread_us=spread * 1e6, b_spread_us=(max(rb) - min(rb)) * 1e6, b_over_a=med_b / med_a, target_met=bool(med_b <= med_a + spread))
 
 
+def measure_upload(lens, repeats, reps):
+    """the per-frame loop of a live renderer (INTEGRATION.md "Plates that are frame buffers"): upload the displayed plates, apply one frame.
+    A = full uploads (bk_upload_plate_rgba_device), B = footprint uploads (bk_upload_plate_rgba_footprint_device), P = the one-frame apply
+    behind either.  Frame k goes to truecolour globe k % 16 from source set k % 4, so neither globe nor source is in the Infinity Cache when
+    its turn comes again; a 1 GiB fill in front of every timed frame keeps the GPU busy while the host enqueues the frame's launches, so the
+    events time the kernels and not the host.  `repeats` blocks of `reps` frames each, A and B alternated frame by frame."""
+    G, SETS = SLOTS // 4, 4
+    ctx = blinky_amd.Context(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_frames(SLOTS)
+    S.configure(ctx, "cube", lens, None, (W, H))
+    display, _ = ctx.build()
+    ps = min(W, H)
+    shown = [p for p in range(6) if p < len(display) and display[p]]
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    src = [[torch.randint(0, 256, (ps, ps, 4), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(6)] for _ in range(SETS)]
+    pitch = 4 * ps
+    assert all(t.data_ptr() % 16 == 0 for s in src for t in s) and pitch % 16 == 0
+    out = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")
+    plug = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+
+    def full(g, s):
+        for p in shown:
+            ctx.upload_plate_rgba_device(g, p, src[s][p].data_ptr(), pitch)
+
+    def foot(g, s):
+        for p in shown:
+            ctx.upload_plate_rgba_footprint_device(g, p, src[s][p].data_ptr(), pitch)
+
+    def apply(g):
+        ctx.apply_rgba_device(out.data_ptr(), 4 * W, 4 * W * H, globe0=g, nframes=1)
+
+    # before anything is timed: the frame after B (over another source's texels) must be the frame after A, byte for byte
+    fp = [ctx.plate_footprint(p) for p in range(6)]
+    full(0, 0)
+    apply(0)
+    torch.cuda.synchronize()
+    frame_a = out.clone()
+    full(1, 1)
+    foot(1, 0)
+    out.zero_()
+    apply(1)
+    torch.cuda.synchronize()
+    if not torch.equal(out, frame_a):
+        raise SystemExit(f"{lens}: the frame after the footprint upload differs from the frame after the full upload in {int((out != frame_a).sum())} bytes - nothing timed")
+    del frame_a
+    for k in range(2 * G):                                 # warm-up: every globe through both uploads, the block map compiled and tuned
+        (full if k % 2 else foot)(k % G, k % SETS)
+        apply(k % G)
+    torch.cuda.synchronize()
+    blocks = {"a": [], "b": [], "pa": [], "pb": [], "ap": [], "bp": []}
+    k = 0
+    for _ in range(repeats):
+        ev = []
+        for r in range(2 * reps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            plug.fill_(r & 255)
+            e[0].record(stream)
+            (foot if r % 2 else full)(k % G, k % SETS)
+            e[1].record(stream)
+            apply(k % G)
+            e[2].record(stream)
+            ev.append(e)
+            k += 1
+        torch.cuda.synchronize()
+        up = [e[0].elapsed_time(e[1]) * 1e3 for e in ev]
+        ap = [e[1].elapsed_time(e[2]) * 1e3 for e in ev]
+        both = [e[0].elapsed_time(e[2]) * 1e3 for e in ev]
+        for name, xs, odd in (("a", up, 0), ("b", up, 1), ("pa", ap, 0), ("pb", ap, 1), ("ap", both, 0), ("bp", both, 1)):
+            blocks[name].append(statistics.median(xs[odd::2]))
+    ctx.close()
+    med = {n: statistics.median(v) for n, v in blocks.items()}
+    spread = {n: max(v) - min(v) for n, v in blocks.items()}
+    tiles_plate = ((ps + 7) // 8) * ((ps + 15) // 16)
+    tiles = sum(fp[p][1] for p in shown)
+    return dict(lens=lens, W=W, H=H, ps=ps, displayed_plates=shown, frames_per_block=reps, blocks=repeats,
+                footprint_tiles=[fp[p][1] for p in range(6)], footprint_rects=[list(fp[p][0]) for p in range(6)], tiles_per_plate=tiles_plate,
+                tile_ratio=tiles / (tiles_plate * len(shown)),
+                model_bytes_a=8 * 16 * ((ps + 15) // 16) * ps * len(shown), model_bytes_b=8 * 128 * tiles,
+                blocks_us=blocks, median_us=med, spread_us=spread, b_over_a=med["b"] / med["a"], bp_over_ap=med["bp"] / med["ap"],
+                a_gb_s=8 * 16 * ((ps + 15) // 16) * ps * len(shown) / med["a"] / 1e3, b_gb_s=8 * 128 * tiles / med["b"] / 1e3,
+                target_met=bool(med["b"] <= med["a"] + spread["a"]))
+
+
+def main_upload(args):
+    rows = []
+    for lens in args.lenses.split(","):
+        r = measure_upload(lens, args.repeats, max(31, args.reps))
+        rows.append(r)
+        m, s, b = r["median_us"], r["spread_us"], r["blocks_us"]
+        print(f"4K cube/{lens}, one truecolour globe per frame, device plates (16-byte aligned), plates {r['displayed_plates']} displayed; footprint "
+              f"{r['footprint_tiles']} of {r['tiles_per_plate']} tiles per plate (ratio over the displayed plates {r['tile_ratio']:.3f}), "
+              f"{r['blocks']} blocks of {r['frames_per_block']} frames each way, A/B alternated:\n"
+              f"  A  full uploads          {m['a']:8.1f} us (blocks {fmt(b['a'])}; spread {s['a']:.1f})  model {r['model_bytes_a'] / 1e6:.1f} MB -> {r['a_gb_s']:.0f} GB/s\n"
+              f"  B  footprint uploads     {m['b']:8.1f} us (blocks {fmt(b['b'])}; spread {s['b']:.1f})  model {r['model_bytes_b'] / 1e6:.1f} MB -> {r['b_gb_s']:.0f} GB/s\n"
+              f"  P  one-frame apply       {m['pa']:8.1f} us after A, {m['pb']:.1f} us after B (spreads {s['pa']:.1f}, {s['pb']:.1f})\n"
+              f"  A + P {m['ap']:.1f} us, B + P {m['bp']:.1f} us per frame (spreads {s['ap']:.1f}, {s['bp']:.1f}); (B + P) / (A + P) = {r['bp_over_ap']:.3f}\n"
+              f"  frame after B == frame after A; B / A = {r['b_over_a']:.3f} next to the tile ratio {r['tile_ratio']:.3f}; "
+              f"expectation B <= A + A's spread: {'met' if r['target_met'] else 'MISSED'}", flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main_ss2(args):
     rows = []
     what = "tinted" if args.tint else "plain"
@@ -267,9 +383,13 @@ def main():
     ap.add_argument("--out", default=None, help="also write the results as JSON lines to this file")
     ap.add_argument("--tint", action="store_true", help="f_rubix: 8-bit rubix launch A' / tinted truecolour B' / plain truecolour B")
     ap.add_argument("--ss2", action="store_true", help="2x2 supersampling: full-size truecolour launch A (with --tint: the tinted one) / fused ss2 launch B")
+    ap.add_argument("--upload", action="store_true", help="the per-frame loop: full plate uploads A / footprint uploads B / the one-frame apply P behind them")
+    ap.add_argument("--reps", type=int, default=31, help="--upload: frames each way per block (at least 31)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_rgba.py measures on the GPU; there is none here")
+    if args.upload:
+        return main_upload(args)
     if args.ss2:
         return main_ss2(args)
     if args.tint:
