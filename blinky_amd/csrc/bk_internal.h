@@ -41,7 +41,7 @@ struct Span { int row, x0, x1; };
 
 struct Rubix { int numcells = 10; double cell = 4, pad = 1; };   // defaults: fisheye.c:672
 
-struct LensProgram;   // bk_lens.cpp: parsed scripts + hiprtc modules
+struct LensProgram;   // bk_lens_priv.h: parsed scripts + hiprtc modules
 struct CoopMap;       // bk_apply_coop.hip: per-block staging plans of the workgroup-cooperative apply kernel
 struct Resident;      // bk_apply_resident.inc: the resident single-frame apply (its kernel, command ring and stream)
 
@@ -114,7 +114,7 @@ struct bk_ctx {
     hipEvent_t build_time_ev[2] = {nullptr, nullptr};   // bk_build's timing pair, kept (creating and destroying them is four runtime calls a build)
     int *h_build_flags = nullptr;        // pinned: the counters of a forward build's two passes, read back without a stop in between
     bool fwd_tiles_used = false;         // the last build's quad pass went by bk_forward_tiles' flags (bk_debug_forward_tiles)
-    void *fwd_tables = nullptr;          // BkBuildParams::fwd_quot + fwd_uv for platesize fwd_tables_ps (bk_lens.cpp)
+    void *fwd_tables = nullptr;          // BkBuildParams::fwd_quot + fwd_uv for platesize fwd_tables_ps (bk_build.cpp)
     int fwd_tables_ps = -1;
     // bk_debug_set_forward_corners (tests): a host copy of a texel-corner table that the forward build on the device uploads in place
     // of its corner pass
@@ -256,7 +256,7 @@ int resident_info(bk_ctx *ctx, int out[12]);
 inline void resident_quiesce(bk_ctx *ctx) { if (ctx->resident) (void)resident_stop(ctx); }
 bool resident_leaves_room(bk_ctx *ctx);
 void hw_queue_note();      // one line on stderr, once, when GPU_MAX_HW_QUEUES could not be raised for the resident apply (bk_api.cpp)
-/* job(i) for i in [0, parts) on the library's pool of host threads (bk_lens.cpp: the pool that re-derives flagged pixels), the caller
+/* job(i) for i in [0, parts) on the library's pool of host threads (bk_hostpool.cpp: the pool that re-derives flagged pixels), the caller
  * waiting; parts <= 1 or a pool of one thread: on the calling thread */
 void host_parallel(size_t parts, const std::function<void(size_t)> &job);
 bool resident_running(bk_ctx *ctx);      // a session's kernel is on the device right now

@@ -3,7 +3,7 @@ tests/hostemu compiles the very translation unit hiprtc gets as host C++ and run
 
 What must hold: wherever the table built on the portable libm (what the device computes) differs from the table
 the reference computes on the platform libm, the device code has FLAGGED that pixel - so the host fix-up
-(bk_lens.cpp) re-derives it and the final table is the reference's.  And the flagged set stays small."""
+(bk_build.cpp) re-derives it and the final table is the reference's.  And the flagged set stays small."""
 import os
 import sys
 

@@ -10,7 +10,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 mkdir -p "$OUT"
 make -C "$ROOT/blinky_amd/csrc" ARCH=gfx950 >/dev/null
 cd "$ROOT/blinky_amd/csrc"
-for f in bk_api.cpp bk_lens.cpp bk_lua.cpp bk_emit.cpp bk_embed.cpp bk_comm.cpp; do
+for f in bk_api.cpp bk_lens.cpp bk_build.cpp bk_modules.cpp bk_codecache.cpp bk_hostpool.cpp bk_lua.cpp bk_emit.cpp bk_embed.cpp bk_comm.cpp; do
     [ "$OUT/$f.o" -nt "$f" ] && [ "$OUT/$f.o" -nt bk_lua.h ] && [ "$OUT/$f.o" -nt bk_internal.h ] && continue
     $HIPCC --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -fsanitize=address,undefined -fno-gpu-sanitize \
         -fno-omit-frame-pointer -DBK_DEBUG_API=1 -w -c $f -o "$OUT/$f.o"
