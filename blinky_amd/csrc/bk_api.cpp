@@ -157,6 +157,7 @@ extern "C" void bk_destroy(bk_ctx *ctx)
     bk::footprint_free(ctx);
     hipFree(ctx->d_pal);
     hipFree(ctx->d_lut_rgba);
+    hipFree(ctx->d_lut_fb);
     hipFree(ctx->d_display);
     hipFree(ctx->d_flag_list);
     for (void *q : ctx->fwd_scratch) hipFree(q);
@@ -803,17 +804,27 @@ extern "C" int bk_apply_rgba_device(bk_ctx *ctx, int globe0, int nframes, void *
 }
 
 // the device copy of a truecolour launch's byte LUTs, kept as upload_pal keeps the 8-bit palette: while the bytes AND the stream are
-// the same.  A buffer of its own - ctx->d_pal and its cache stay what the last 8-bit rubix launch made them.
+// the same.  The buffer, its cache, stream and flag are the caller's: the staged launches have one set (upload_lut_rgba; ctx->d_pal and its
+// cache stay what the last 8-bit rubix launch made them), bk_apply_rgba_fb_device another (upload_lut_fb), so neither disturbs the other's.
+static int upload_lut(bk_ctx *ctx, const uint8_t lut[4][BK_MAX_PLATES][256], uint8_t **d_lut, uint8_t *cache, hipStream_t *stream, bool *cached)
+{
+    const size_t bytes = 4 * BK_MAX_PLATES * 256;
+    if (!*d_lut) BK_HIP(ctx, hipMalloc((void **)d_lut, bytes));
+    if (*cached && *stream == ctx->stream && memcmp(cache, lut, bytes) == 0) return BK_OK;
+    *cached = false;
+    BK_HIP(ctx, hipMemcpyAsync(*d_lut, lut, bytes, hipMemcpyHostToDevice, ctx->stream));
+    memcpy(cache, lut, bytes);
+    *stream = ctx->stream;
+    *cached = true;
+    return BK_OK;
+}
 static int upload_lut_rgba(bk_ctx *ctx, const uint8_t lut[4][BK_MAX_PLATES][256])
 {
-    if (!ctx->d_lut_rgba) BK_HIP(ctx, hipMalloc((void **)&ctx->d_lut_rgba, sizeof ctx->lut_rgba_cache));
-    if (ctx->lut_rgba_cached && ctx->lut_rgba_stream == ctx->stream && memcmp(ctx->lut_rgba_cache, lut, sizeof ctx->lut_rgba_cache) == 0) return BK_OK;
-    ctx->lut_rgba_cached = false;
-    BK_HIP(ctx, hipMemcpyAsync(ctx->d_lut_rgba, lut, sizeof ctx->lut_rgba_cache, hipMemcpyHostToDevice, ctx->stream));
-    memcpy(ctx->lut_rgba_cache, lut, sizeof ctx->lut_rgba_cache);
-    ctx->lut_rgba_stream = ctx->stream;
-    ctx->lut_rgba_cached = true;
-    return BK_OK;
+    return upload_lut(ctx, lut, &ctx->d_lut_rgba, ctx->lut_rgba_cache, &ctx->lut_rgba_stream, &ctx->lut_rgba_cached);
+}
+static int upload_lut_fb(bk_ctx *ctx, const uint8_t lut[4][BK_MAX_PLATES][256])
+{
+    return upload_lut(ctx, lut, &ctx->d_lut_fb, ctx->lut_fb_cache, &ctx->lut_fb_stream, &ctx->lut_fb_cached);
 }
 
 // bk_apply_rgba_device with rubix: byte c of a mapped pixel of tint t < BK_MAX_PLATES leaves as lut[c][t][v]
@@ -842,6 +853,38 @@ extern "C" int bk_apply_rgba_ss2_device(bk_ctx *ctx, int globe0, int nframes, vo
         if (int r = upload_lut_rgba(ctx, lut)) return r;
     uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0 / 2) * dst_pitch + (size_t)x0 * 4;
     return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride, lut ? ctx->d_lut_rgba : nullptr, true);
+}
+
+// ---- truecolour straight from the renderer's frame buffers (bk_apply_rgba_fb.inc) ----------------------------------------------
+// one truecolour frame out of six row-major 32-bit plates in device memory: no ring slot, no block map, either apply variant
+extern "C" int bk_apply_rgba_fb_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES], void *dst_dev,
+                                       int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256], int ss2)
+{
+    static const char *who = "bk_apply_rgba_fb_device";
+    if (!ctx || !plates_dev || !plate_pitch_bytes || !dst_dev) return BK_E_INVALID;
+    if (ctx->device < 0) return ctx->fail(BK_E_STATE, "%s: this context was created without a device (BK_DEVICE_NONE)", who);
+    if (!ctx->lensmap_valid || !ctx->d_offsets) return ctx->fail(BK_E_STATE, "%s: no lensmap (bk_build / bk_set_lensmap first)", who);
+    if (ss2 != 0 && ss2 != 1) return ctx->fail(BK_E_INVALID, "%s: ss2 is 0 or 1, not %d", who, ss2);
+    const long long width = ss2 ? ((long long)ctx->W + 1) / 2 : (long long)ctx->W;
+    if (x0 < 0 || y0 < 0 || (long long)dst_pitch < 4ll * (width + x0)) return ctx->fail(BK_E_INVALID, "%s: bad pitch/origin", who);
+    if (ss2 && ((ctx->row0 & 1) || ((ctx->row1 & 1) && ctx->row1 != ctx->H)))
+        return ctx->fail(BK_E_STATE, "%s: the owned rows [%d, %d) cut a 2x2 quad: row0 must be even and row1 even or the frame's height (bk_set_rows)", who,
+                         ctx->row0, ctx->row1);
+    if (((uintptr_t)dst_dev | (uintptr_t)dst_pitch) & 3u) return ctx->fail(BK_E_INVALID, "%s: dst and its pitch must be multiples of 4 bytes", who);
+    for (int p = 0; p < BK_MAX_PLATES; ++p)
+        if (plates_dev[p] && ((((uintptr_t)plates_dev[p] | (uintptr_t)plate_pitch_bytes[p]) & 3u) || (long long)plate_pitch_bytes[p] < 4ll * ctx->ps))
+            return ctx->fail(BK_E_INVALID, "%s: plate %d: the address and the pitch (%d) must be multiples of 4 bytes, the pitch at least 4 * %d", who, p,
+                             plate_pitch_bytes[p], ctx->ps);
+    if (int r = ensure_device(ctx)) return r;                // (ends a resident session, as every device entry point)
+    if (int r = footprint_ready(ctx, who)) return r;         // (cached; one pass and one host synchronisation after the lensmap or the rows changed)
+    for (int p = 0; p < BK_MAX_PLATES; ++p)
+        if (!plates_dev[p] && ctx->fp_summary(p)[0] != 0)
+            return ctx->fail(BK_E_INVALID, "%s: plate %d is NULL, but the lensmap reads %d of its tiles (bk_plate_footprint)", who, p, ctx->fp_summary(p)[0]);
+    bk::Range range(who);
+    if (lut)
+        if (int r = upload_lut_fb(ctx, lut)) return r;
+    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + (ss2 ? ctx->row0 / 2 : ctx->row0)) * dst_pitch + (size_t)x0 * 4;
+    return bk::launch_apply_rgba_fb(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->d_lut_fb : nullptr, ss2 != 0);
 }
 
 // ---- resident single-frame apply (bk_apply_resident.inc) ------------------------------------------------------------

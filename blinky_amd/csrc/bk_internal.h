@@ -97,6 +97,7 @@ struct bk_ctx {
     uint8_t *d_frame = nullptr;      // [row1-row0][W] staging for bk_apply (host dst)
     uint8_t *d_pal = nullptr;        // [6][256]
     uint8_t *d_lut_rgba = nullptr;   // [4][6][256] the byte LUTs of bk_apply_rgba_tinted_device; a buffer of its own (d_pal stays the 8-bit palette), allocated on first use
+    uint8_t *d_lut_fb = nullptr;     // [4][6][256] the byte LUTs of bk_apply_rgba_fb_device: its own buffer and cache (upload_lut_fb), allocated on first use
     uint64_t *d_mask = nullptr;      // mapped bits, 1 per pixel of the owned rows
     int *d_display = nullptr;        // [6] display flags + [1] error bits + [1] flagged-entry count + [1] first malformed result (scan key + 1) written by the build kernels
     unsigned int last_bad_key = 0;   // of the last bk_build: 1 + scan key of the first pixel whose callback returned a malformed result (0 = none)
@@ -165,6 +166,9 @@ struct bk_ctx {
     uint8_t lut_rgba_cache[4 * BK_MAX_PLATES * 256] = {};   // what d_lut_rgba holds, uploaded on lut_rgba_stream (upload_lut_rgba)
     hipStream_t lut_rgba_stream = nullptr;
     bool lut_rgba_cached = false;
+    uint8_t lut_fb_cache[4 * BK_MAX_PLATES * 256] = {};     // what d_lut_fb holds, uploaded on lut_fb_stream
+    hipStream_t lut_fb_stream = nullptr;
+    bool lut_fb_cached = false;
     bool res_rubix = false;
     bool apply_was_resident = false;      // latched by bk_apply_begin: the frame in flight went to the resident kernel
     bk::LensProgram *prog = nullptr;      // owned; freed with bk::lensprogram_free
@@ -235,6 +239,10 @@ int launch_apply_coop(bk_ctx *ctx, int frame0, int nframes, uint8_t *dst_first_o
 // ss2: 2x2 supersampling into half-size frames (bk_apply_rgba_ss2_device) - dst is then row row0 / 2 of the half-size frame
 int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch, size_t frame_stride,
                       const uint8_t *d_lut = nullptr, bool ss2 = false);
+// bk_apply_rgba_fb.inc (part of bk_apply_coop.hip): one truecolour frame straight out of six row-major 32-bit plates in device memory
+// (a NULL plate: one that no lensmap entry of the owned rows names); dst = the first owned row at the origin; ss2: of the half-size frame
+int launch_apply_rgba_fb(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
+                         const uint8_t *d_lut, bool ss2);
 int coopmap_stats(bk_ctx *ctx, int out[6]);   // blocks, direct-gather blocks, empty blocks, LDS bytes per buffer
 int coopmap_traffic_model(bk_ctx *ctx, uint64_t out[8]);
 int coopmap_xcd_probe(bk_ctx *ctx, int *out, int nwg);

@@ -81,6 +81,8 @@ _SIGS = {
     "bk_apply_rgba_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i]),
     "bk_apply_rgba_tinted_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
     "bk_apply_rgba_ss2_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
+    "bk_apply_rgba_fb_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp, _i]),
+    "bk_debug_fb_decode_check": (C.c_longlong, [_i, _i]),
     "bk_globe_device_ptr": (_vp, [_vp, _i]),
     "bk_fill_plate_lcg": (_i, [_vp, _i, _i, C.c_uint32]),
     "bk_apply": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
@@ -487,6 +489,21 @@ class Context:
             if lut.shape != (4, MAX_PLATES, 256):
                 raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
         self._chk(lib.bk_apply_rgba_ss2_device(self._h, globe0, nframes, dst_ptr, pitch, frame_stride, x0, y0, _ptr(lut)))
+
+    def apply_rgba_fb_device(self, plates, pitches, dst_ptr, dst_pitch, x0=0, y0=0, lut=None, ss2=False):
+        """one truecolour frame straight out of six row-major 32-bit plates in device memory (a renderer's frame buffers): no upload, no
+        ring slot, no block map.  plates: six device addresses (int / c_void_p; None for a plate whose footprint is empty), pitches:
+        their row pitches in bytes; lut None: plain, else uint8 [4][6][256]; ss2: the 2x2-supersampled half-size frame.  The frame is
+        byte for byte what upload_plate_rgba_device + apply_rgba_device / _tinted_device / _ss2_device write"""
+        if len(plates) != MAX_PLATES or len(pitches) != MAX_PLATES:
+            raise ValueError(f"plates and pitches must have {MAX_PLATES} entries")
+        pp = (_vp * MAX_PLATES)(*[p.value if isinstance(p, C.c_void_p) else p for p in plates])
+        pi = (_i * MAX_PLATES)(*[int(p) for p in pitches])
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8)
+            if lut.shape != (4, MAX_PLATES, 256):
+                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        self._chk(lib.bk_apply_rgba_fb_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut), int(ss2)))
 
     # ---- the resident single-frame apply (bk_apply_resident_*): one kernel stays on the device, frames are commands
     def resident_begin(self, rubix_on=False, pal=None, idle_ms=0.0):

@@ -22,7 +22,8 @@
  *   - texels and pixels are 8-bit palettised, as the reference's (TyrQuake's software rasteriser).  TRUECOLOUR - 32-bit plates
  *     warped into 32-bit frames, for hosts whose plates are frame buffers of a present-day renderer - is bk_upload_plate_rgba /
  *     bk_upload_plate_rgba_device / bk_plate_footprint / bk_upload_plate_rgba_footprint / bk_upload_plate_rgba_footprint_device /
- *     bk_apply_rgba_device / bk_apply_rgba_tinted_device / bk_apply_rgba_ss2_device: a 32-bit globe is four byte planes in four consecutive slots of the same
+ *     bk_apply_rgba_device / bk_apply_rgba_tinted_device / bk_apply_rgba_ss2_device / bk_apply_rgba_fb_device (one frame straight out
+ *     of the frame buffers, no globe at all): a 32-bit globe is four byte planes in four consecutive slots of the same
  *     globe ring, so lens build, lensmap and everything else in this header are shared with the 8-bit path as they are.
  */
 #ifndef BLINKY_HIP_H
@@ -327,6 +328,42 @@ int bk_apply_rgba_tinted_device(bk_ctx *ctx, int globe0, int nframes, void *dst_
 int bk_apply_rgba_ss2_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch,
                              size_t frame_stride, int x0, int y0,
                              const uint8_t lut[4][BK_MAX_PLATES][256] /* nullable: NULL = plain, else tinted */);
+/* bk_apply_rgba_fb_device: ONE truecolour frame warped straight out of the renderer's six frame buffers - no upload into byte planes,
+ * no ring slot, no block map.  For the host the footprint upload was built for: fresh 32-bit plates every frame, one warped frame back.
+ * Source: plates_dev[p] is the address of texel (0, 0) of plate p in device memory, a plate ps rows of ps 32-bit texels, rows
+ * plate_pitch_bytes[p] apart.  The bytes are opaque, as everywhere in the truecolour API.  An address and its pitch must be multiples
+ * of 4 and the pitch at least 4 * ps, otherwise BK_E_INVALID; multiples of 16 are the recommended class (a renderer's frame buffer,
+ * as for bk_upload_plate_rgba_device).  Plates may share one allocation (an atlas) or have six different pitches.
+ * NULL plates: a plate whose footprint is empty - bk_plate_footprint's ntiles == 0, equivalently bk_build's display flag clear for
+ * the owned rows - may be NULL, and its pitch is then ignored; a NULL plate with a non-empty footprint is BK_E_INVALID.  The check
+ * uses the cached footprint: the first call after the lensmap or the owned rows changed pays the footprint's one pass over the lensmap
+ * and one host synchronisation, every later call nothing.
+ * THE CONTRACT ON READS: only texels that some lensmap entry of the owned rows names are read - a subset of the footprint's tiles, so
+ * SOURCE TEXELS OUTSIDE rect ARE NEVER READ and a renderer that scissored to bk_plate_footprint's rect is served.  Whatever writes
+ * the plates must be ordered before the call on the context's stream (or be complete), and the plates stay untouched until the launch
+ * has run.
+ * Result: the frame is byte for byte what the existing calls write after bk_upload_plate_rgba_device of the same six plates into a
+ * globe - ss2 == 0, lut == NULL: bk_apply_rgba_device(nframes = 1); ss2 == 0, lut given: bk_apply_rgba_tinted_device; ss2 == 1:
+ * bk_apply_rgba_ss2_device with the same lut (NULL or given).  Addressing, x0 / y0 in pixels, owned rows only and untouched unmapped
+ * pixels are as documented there; tints >= BK_MAX_PLATES leave the texel as it is; ss2 is the exact (sum + n/2) / n over the mapped
+ * samples, the tint applied per sample before the average, into the half-size frame of Wo = (W + 1) / 2 pixels a row, and needs row0
+ * even and row1 even or H (BK_E_STATE otherwise).  ss2 outside {0, 1} is BK_E_INVALID.
+ * Destination: the rules of bk_apply_rgba_device - dst_dev and dst_pitch multiples of 4 required, dst_dev + 4 * x0 and dst_pitch
+ * multiples of 16 give 16-byte stores; dst_pitch >= 4 * (W + x0), ss2: 4 * (Wo + x0); a negative origin is BK_E_INVALID.
+ * Other errors: BK_E_INVALID for a NULL ctx, plates_dev, plate_pitch_bytes or dst_dev; BK_E_STATE without a lensmap and for a
+ * BK_DEVICE_NONE context.  Asynchronous on the context's stream; ends a resident session first, as every other device entry point.
+ * It needs no ring slots (bk_set_frames(1) will do), works under bk_set_apply_variant(0) too, and compiles and tunes nothing: it
+ * touches neither block map, their tuning state nor the staged launches' LUT copy (its own 6144-byte copy is kept while the bytes and
+ * the stream stay the same), so alternating with any other launch recompiles and re-uploads nothing of theirs.
+ * Measured at 3840x2160 from plates in HBM (tools/bench_rgba.py --fb, profiles/rgba_fb_apply.txt), against footprint uploads of the
+ * displayed plates plus the one-frame bk_apply_rgba_device: cube/panini 38.6 us against 65.2, cube/hammer 61.8 against 117.8; tinted
+ * 45.3 / 72.0 and 63.2 / 128.2; ss2 45.1 / 61.0 and 67.8 / 110.6 - and it saves the 112.8 MB of ring a 4K globe takes.  The staged
+ * apply ALONE is faster (27.6 and 40.6 us plain): a host whose globes stay resident for many frames stays with bk_apply_rgba_device.
+ * Out of scope: more than one frame per call; a host-pointer form; the resident kernel; the bk_comm_* / bk_multi_* exchanges (stripe
+ * CONTEXTS - bk_set_rows - do work); the drop-in fisheye_hip.c, whose engine is 8-bit; texel filtering (one nearest texel per sample). */
+int bk_apply_rgba_fb_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
+                            void *dst_dev, int dst_pitch, int x0, int y0,
+                            const uint8_t lut[4][BK_MAX_PLATES][256] /* nullable: NULL = plain, else tinted */, int ss2);
 
 /* ---- resident single-frame apply ------------------------------------------------------------------------------------
  * replaces: the per-frame call of render_lensmap (fisheye.c:803 -> 2406-2424) for hosts whose globes stay in device memory.

@@ -125,6 +125,12 @@ int         bk_debug_stripe_bounds(const uint32_t *row_cost, int H, int W, int n
 /* what bk_comm_rebalance / bk_multi_rebalance sum over the ranks: the cost of every row of this context's stripe to its apply
  * variant (host uint32 [H], rows of other stripes 0); needs a built lensmap */
 int         bk_debug_row_costs(bk_ctx *ctx, uint32_t *host_out);
+/* test hook, no device needed: how bk_apply_rgba_fb_device's kernel turns a lensmap entry back into (plate, px, py) - comparisons, a
+ * host-made reciprocal and one correction step instead of bk_texel_coords' divisions - against bk_texel_coords itself, for a globe whose
+ * padded plates are gp x ph: one texel of every 128-byte tile of the last plate (what happens inside a plate does not depend on the plate)
+ * and the first and last two tiles of every plate, where the comparisons decide.  -> the number of texels that decode differently
+ * (0 = exact), -1 for a layout bk_resize does not accept (gp no multiple of 64, ph none of 8 or above gp, 6 * gp * ph >= 2^32 - 1) */
+long long   bk_debug_fb_decode_check(int gp, int ph);
 
 #ifdef __cplusplus
 }

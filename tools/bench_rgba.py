@@ -7,7 +7,7 @@ At 3840x2160 cube/panini and cube/hammer, over the 64-slot LCG ring of the bench
 B's output is compared with A's plane by plane before anything is timed.  Timing: HIP events on the context's stream, warm-up
 launches first, regions of at least --region seconds made of ten event-timed trains of launches (a region's figure is the median
 train), A / B / A / B ... alternated --repeats times inside this one process.  The target: B's median <= A's median + A's own spread
-(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2] [--upload]
+(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2] [--upload] [--fb]
 
 --tint: the same protocol for f_rubix on truecolour frames, three launches alternated A' / B' / B:
   A'  one bk_apply_device launch of 64 8-bit frames with rubix_on = 1 (existing code: the same bytes through the same number of LUT
@@ -30,7 +30,17 @@ The frame after B must equal the frame after A byte for byte before anything is 
 sets of source plates (out of the Infinity Cache by the time their turn comes again), A and B alternate frame by frame, --repeats blocks of
 --reps frames each way; a figure is the median of the block medians, its spread their max - min.  Printed with the footprint's tile
 count and the byte model (8 bytes per texel of every chunk / tile written).  The expectations: cube/hammer (footprint = everything)
-B <= A + A's spread; cube/panini B / A reported next to the tile ratio."""
+B <= A + A's spread; cube/panini B / A reported next to the tile ratio.
+
+--fb [--tint] [--ss2] [--reps 31]: the same live renderer with and without the globe, alternated frame by frame:
+  B + P  bk_upload_plate_rgba_footprint_device of every displayed plate, then the one-frame bk_apply_rgba_device (--tint:
+         bk_apply_rgba_tinted_device, --ss2: bk_apply_rgba_ss2_device, with --tint through the same tables) - existing code
+  D      bk_apply_rgba_fb_device straight from the same plates: no upload, no globe, no block map
+D's frame must equal B + P's byte for byte before anything is timed.  The source is a ring of 16 sets of six device plates (1.8 GB at 4K,
+16-byte aligned) advanced every frame, so the texels come from HBM and not from the Infinity Cache; B + P also rotates through 16
+truecolour globes.  --repeats blocks of --reps frames each way; a figure is the median of the block medians, its spread their max - min.
+The expectation: D < B + P by more than the two spreads together; D against P alone is printed beside it (what a caller whose globes
+stay resident would pay)."""
 import argparse
 import json
 import os
@@ -315,6 +325,137 @@ def measure_upload(lens, repeats, reps):
                 target_met=bool(med["b"] <= med["a"] + spread["a"]))
 
 
+def measure_fb(lens, repeats, reps, tint, ss2):
+    """B + P (footprint uploads into a globe + the one-frame staged apply) against D (bk_apply_rgba_fb_device from the same plates), frame
+    by frame.  Frame k reads source set k % 16 (and, B + P, writes truecolour globe k % 16): by the time a set's turn comes again 1.7 GB of
+    other plates and a 1 GiB fill have passed through the Infinity Cache.  The fill in front of every timed frame also keeps the GPU busy
+    while the host enqueues the frame's launches, so the events time the kernels and not the host."""
+    G = SETS = SLOTS // 4
+    ctx = blinky_amd.Context(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_frames(SLOTS)
+    S.configure(ctx, "cube", lens, None, (W, H))
+    display, _ = ctx.build()
+    ps = min(W, H)
+    shown = [p for p in range(6) if p < len(display) and display[p]]
+    lut = None
+    if tint:
+        pal = blinky_amd.ffi.create_palmap(((np.arange(768) * 37) % 256).astype(np.uint8))
+        lut = np.ascontiguousarray(np.broadcast_to(pal, (4, 6, 256)))
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    src = [[torch.randint(0, 256, (ps, ps, 4), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(6)] for _ in range(SETS)]
+    pitch = 4 * ps
+    assert all(t.data_ptr() % 16 == 0 for s in src for t in s) and pitch % 16 == 0
+    ptrs = [[src[s][p].data_ptr() if p in shown else None for p in range(6)] for s in range(SETS)]
+    pitches = [pitch] * 6
+    Wd, Hd = ((W + 1) // 2, (H + 1) // 2) if ss2 else (W, H)
+    out = torch.zeros((Hd, Wd, 4), dtype=torch.uint8, device="cuda")
+    plug = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+
+    def foot(g, s):
+        for p in shown:
+            ctx.upload_plate_rgba_footprint_device(g, p, src[s][p].data_ptr(), pitch)
+
+    def staged(g):
+        if ss2:
+            ctx.apply_rgba_ss2_device(out.data_ptr(), 4 * Wd, 4 * Wd * Hd, globe0=g, nframes=1, lut=lut)
+        elif tint:
+            ctx.apply_rgba_tinted_device(out.data_ptr(), 4 * Wd, 4 * Wd * Hd, lut, globe0=g, nframes=1)
+        else:
+            ctx.apply_rgba_device(out.data_ptr(), 4 * Wd, 4 * Wd * Hd, globe0=g, nframes=1)
+
+    def direct(s):
+        ctx.apply_rgba_fb_device(ptrs[s], pitches, out.data_ptr(), 4 * Wd, lut=lut, ss2=ss2)
+
+    # before anything is timed: D's frame must be B + P's, byte for byte - at full size, plain, and in the flavour that is timed
+    fp = [ctx.plate_footprint(p) for p in range(6)]
+    full_out = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")
+    foot(0, 0)
+    ctx.apply_rgba_device(full_out.data_ptr(), 4 * W, 4 * W * H, globe0=0, nframes=1)
+    torch.cuda.synchronize()
+    frame_bp = full_out.clone()
+    full_out.zero_()
+    ctx.apply_rgba_fb_device(ptrs[0], pitches, full_out.data_ptr(), 4 * W)
+    torch.cuda.synchronize()
+    if not torch.equal(full_out, frame_bp):
+        raise SystemExit(f"{lens}: the frame from the frame buffers differs from the frame after upload + apply in {int((full_out != frame_bp).sum())} bytes - nothing timed")
+    del full_out, frame_bp
+    staged(0)
+    torch.cuda.synchronize()
+    frame_bp = out.clone()
+    out.zero_()
+    direct(0)
+    torch.cuda.synchronize()
+    if not torch.equal(out, frame_bp):
+        raise SystemExit(f"{lens}: the timed flavour's frame from the frame buffers differs from the existing path's in {int((out != frame_bp).sum())} bytes - nothing timed")
+    del frame_bp
+    for k in range(2 * G):                                 # warm-up: every globe and every set once each way, the block map compiled and tuned
+        if k % 2:
+            direct(k % SETS)
+        else:
+            foot(k % G, k % SETS)
+            staged(k % G)
+    torch.cuda.synchronize()
+    blocks = {"b": [], "p": [], "bp": [], "d": []}
+    k = 0
+    for _ in range(repeats):
+        ev = []
+        for r in range(2 * reps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            plug.fill_(r & 255)
+            e[0].record(stream)
+            if r % 2:
+                direct(k % SETS)
+                e[1].record(stream)
+            else:
+                foot(k % G, k % SETS)
+                e[1].record(stream)
+                staged(k % G)
+            e[2].record(stream)
+            ev.append(e)
+            k += 1
+        torch.cuda.synchronize()
+        blocks["b"].append(statistics.median(e[0].elapsed_time(e[1]) * 1e3 for e in ev[0::2]))
+        blocks["p"].append(statistics.median(e[1].elapsed_time(e[2]) * 1e3 for e in ev[0::2]))
+        blocks["bp"].append(statistics.median(e[0].elapsed_time(e[2]) * 1e3 for e in ev[0::2]))
+        blocks["d"].append(statistics.median(e[0].elapsed_time(e[1]) * 1e3 for e in ev[1::2]))
+    off, _ = ctx.read_lensmap()
+    mapped = int((np.asarray(off) != 0xFFFFFFFF).sum())
+    del off
+    ctx.close()
+    med = {n: statistics.median(v) for n, v in blocks.items()}
+    spread = {n: max(v) - min(v) for n, v in blocks.items()}
+    tiles = sum(fp[p][1] for p in shown)
+    # the issue's estimate of D's bytes: the lensmap once, every mapped pixel (ss2: every quad) stored once, the footprint's tiles once
+    model_d = 4 * W * H + (1 if tint else 0) * W * H + 4 * (mapped // 4 if ss2 else mapped) + 4 * 128 * tiles
+    return dict(lens=lens, W=W, H=H, ps=ps, tint=bool(tint), ss2=bool(ss2), displayed_plates=shown, frames_per_block=reps, blocks=repeats,
+                footprint_tiles=[fp[p][1] for p in range(6)], mapped_pixels=mapped, model_bytes_d=model_d,
+                blocks_us=blocks, median_us=med, spread_us=spread, d_over_bp=med["d"] / med["bp"], d_over_p=med["d"] / med["p"],
+                d_model_gb_s=model_d / med["d"] / 1e3, target_met=bool(med["d"] + spread["d"] + spread["bp"] < med["bp"]))
+
+
+def main_fb(args):
+    rows = []
+    what = ("ss2 " if args.ss2 else "") + ("tinted" if args.tint else "plain")
+    for lens in args.lenses.split(","):
+        r = measure_fb(lens, args.repeats, max(31, args.reps), args.tint, args.ss2)
+        rows.append(r)
+        m, s, b = r["median_us"], r["spread_us"], r["blocks_us"]
+        print(f"4K cube/{lens}, one {what} truecolour frame per call from device plates (16-byte aligned, a ring of 16 sets), plates {r['displayed_plates']} "
+              f"displayed, footprint {r['footprint_tiles']} tiles, {r['blocks']} blocks of {r['frames_per_block']} frames each way, B + P / D alternated:\n"
+              f"  B      footprint uploads        {m['b']:8.1f} us (blocks {fmt(b['b'])}; spread {s['b']:.1f})\n"
+              f"  P      one-frame staged apply   {m['p']:8.1f} us (blocks {fmt(b['p'])}; spread {s['p']:.1f})\n"
+              f"  B + P                           {m['bp']:8.1f} us (blocks {fmt(b['bp'])}; spread {s['bp']:.1f})\n"
+              f"  D      bk_apply_rgba_fb_device  {m['d']:8.1f} us (blocks {fmt(b['d'])}; spread {s['d']:.1f})  estimate {r['model_bytes_d'] / 1e6:.1f} MB -> {r['d_model_gb_s']:.0f} GB/s\n"
+              f"  D == B + P byte for byte; D / (B + P) = {r['d_over_bp']:.3f}, D / P = {r['d_over_p']:.3f}; "
+              f"expectation D < B + P by more than both spreads: {'met' if r['target_met'] else 'MISSED'}", flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main_upload(args):
     rows = []
     for lens in args.lenses.split(","):
@@ -384,10 +525,13 @@ def main():
     ap.add_argument("--tint", action="store_true", help="f_rubix: 8-bit rubix launch A' / tinted truecolour B' / plain truecolour B")
     ap.add_argument("--ss2", action="store_true", help="2x2 supersampling: full-size truecolour launch A (with --tint: the tinted one) / fused ss2 launch B")
     ap.add_argument("--upload", action="store_true", help="the per-frame loop: full plate uploads A / footprint uploads B / the one-frame apply P behind them")
-    ap.add_argument("--reps", type=int, default=31, help="--upload: frames each way per block (at least 31)")
+    ap.add_argument("--fb", action="store_true", help="one frame per call: footprint uploads + the staged one-frame apply B + P / bk_apply_rgba_fb_device D (with --tint / --ss2: the matching pairs)")
+    ap.add_argument("--reps", type=int, default=31, help="--upload / --fb: frames each way per block (at least 31)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_rgba.py measures on the GPU; there is none here")
+    if args.fb:
+        return main_fb(args)
     if args.upload:
         return main_upload(args)
     if args.ss2:
