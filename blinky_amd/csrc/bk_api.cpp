@@ -129,6 +129,7 @@ static void free_maps(bk_ctx *ctx)
 {
     hipFree(ctx->d_offsets); ctx->d_offsets = nullptr;
     hipFree(ctx->d_tints); ctx->d_tints = nullptr;
+    hipFree(ctx->d_subtexel); ctx->d_subtexel = nullptr; ctx->subtexel_valid = false;
     hipFree(ctx->d_convert); ctx->d_convert = nullptr;
     hipFree(ctx->d_frame); ctx->d_frame = nullptr;
     hipFree(ctx->d_mask); ctx->d_mask = nullptr;
@@ -238,6 +239,7 @@ void bk::empty_context(bk_ctx *ctx)
     ctx->W = ctx->H = ctx->ps = ctx->gp = ctx->ph = 0;
     ctx->row0 = ctx->row1 = 0;
     ctx->lensmap_valid = false;
+    ctx->subtexel_valid = false;
     ctx->spans_valid = false;
     ctx->err = msg;
 }
@@ -271,6 +273,7 @@ extern "C" int bk_resize(bk_ctx *ctx, int width, int height)
     ctx->W = width; ctx->H = height; ctx->ps = ps; ctx->gp = gp; ctx->ph = ph;
     ctx->row0 = 0; ctx->row1 = height;
     ctx->lensmap_valid = false;
+    ctx->subtexel_valid = false;
     bk::footprint_invalidate(ctx);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail_empty(ctx->fail(BK_E_HIP, "bk_resize: hipStreamSynchronize failed"));
     (void)hipFree(ctx->d_plate_stage);
@@ -298,6 +301,7 @@ extern "C" int bk_set_rows(bk_ctx *ctx, int row0, int row1)
     if (row0 == ctx->row0 && row1 == ctx->row1) return BK_OK;
     ctx->row0 = row0; ctx->row1 = row1;
     ctx->lensmap_valid = false;
+    ctx->subtexel_valid = false;
     ctx->spans_valid = false;
     bk::footprint_invalidate(ctx);
     return alloc_maps(ctx);
@@ -445,11 +449,64 @@ extern "C" int bk_set_lensmap(bk_ctx *ctx, const uint32_t *offsets, const uint8_
     if (int r = bk::launch_convert_offsets(ctx, ctx->d_offsets, px, 1)) return r;      // reference -> padded layout
     if (tints) BK_HIP(ctx, hipMemcpyAsync(ctx->d_tints, tints, px, hipMemcpyHostToDevice, ctx->stream));
     else BK_HIP(ctx, hipMemsetAsync(ctx->d_tints, 255, px, ctx->stream));
+    // a table from outside says nothing about where in its texels the rays land: every entry at the centre until
+    // bk_set_lensmap_subtexel says otherwise
+    if (int r = bk::subtexel_alloc(ctx)) return r;
+    if (ctx->d_subtexel) BK_HIP(ctx, hipMemsetAsync(ctx->d_subtexel, 0x80, px * 2, ctx->stream));
     BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->lensmap_valid = true;
+    ctx->subtexel_valid = ctx->d_subtexel != nullptr;
     ctx->spans_valid = false;
     bk::coopmap_invalidate(ctx);
     bk::footprint_invalidate(ctx);
+    return BK_OK;
+}
+
+// ---- the sub-texel plane (bk_set_subtexel) ---------------------------------------------
+// allocated for the owned rows as they are now; alloc_maps frees it with the maps it lies beside
+int bk::subtexel_alloc(bk_ctx *ctx)
+{
+    if (!ctx->subtexel_on || ctx->d_subtexel || !ctx->map_px) return BK_OK;
+    BK_HIP(ctx, hipMalloc((void **)&ctx->d_subtexel, ctx->map_px * sizeof(uint16_t)));
+    return BK_OK;
+}
+
+extern "C" int bk_set_subtexel(bk_ctx *ctx, int on)
+{
+    if (!ctx) return BK_E_INVALID;
+    if (!on && ctx->d_subtexel) {                   // (nothing of the plane outlives the switch)
+        if (int r = ensure_device(ctx)) return r;
+        BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipFree(ctx->d_subtexel);
+        ctx->d_subtexel = nullptr;
+    }
+    if (!on) ctx->subtexel_valid = false;
+    ctx->subtexel_on = on != 0;
+    return BK_OK;
+}
+
+extern "C" int bk_read_subtexel(bk_ctx *ctx, uint16_t *out)
+{
+    if (!ctx || !out) return BK_E_INVALID;
+    if (!ctx->lensmap_valid) return ctx->fail(BK_E_STATE, "bk_read_subtexel: no lensmap has been built");
+    if (!ctx->subtexel_on) return ctx->fail(BK_E_STATE, "bk_read_subtexel: the sub-texel plane is switched off (bk_set_subtexel)");
+    if (!ctx->subtexel_valid) return ctx->fail(BK_E_STATE, "bk_read_subtexel: the lensmap in place was made before bk_set_subtexel: build or set it again");
+    if (int r = ensure_device(ctx)) return r;
+    BK_HIP(ctx, hipMemcpyAsync(out, ctx->d_subtexel, (size_t)ctx->W * ctx->rows() * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BK_OK;
+}
+
+extern "C" int bk_set_lensmap_subtexel(bk_ctx *ctx, const uint16_t *sub)
+{
+    if (!ctx || !sub) return BK_E_INVALID;
+    if (!ctx->lensmap_valid || !ctx->d_offsets) return ctx->fail(BK_E_STATE, "bk_set_lensmap_subtexel: no lensmap (bk_set_lensmap / bk_build first)");
+    if (!ctx->subtexel_on) return ctx->fail(BK_E_STATE, "bk_set_lensmap_subtexel: the sub-texel plane is switched off (bk_set_subtexel)");
+    if (int r = ensure_device(ctx)) return r;
+    if (int r = bk::subtexel_alloc(ctx)) return r;
+    BK_HIP(ctx, hipMemcpyAsync(ctx->d_subtexel, sub, (size_t)ctx->W * ctx->rows() * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->subtexel_valid = true;
     return BK_OK;
 }
 
@@ -856,11 +913,10 @@ extern "C" int bk_apply_rgba_ss2_device(bk_ctx *ctx, int globe0, int nframes, vo
 }
 
 // ---- truecolour straight from the renderer's frame buffers (bk_apply_rgba_fb.inc) ----------------------------------------------
-// one truecolour frame out of six row-major 32-bit plates in device memory: no ring slot, no block map, either apply variant
-extern "C" int bk_apply_rgba_fb_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES], void *dst_dev,
-                                       int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256], int ss2)
+// the checks the frame-buffer applies share, up to the device being current and the footprint cached
+static int fb_apply_args(bk_ctx *ctx, const char *who, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES], void *dst_dev,
+                         int dst_pitch, int x0, int y0, int ss2)
 {
-    static const char *who = "bk_apply_rgba_fb_device";
     if (!ctx || !plates_dev || !plate_pitch_bytes || !dst_dev) return BK_E_INVALID;
     if (ctx->device < 0) return ctx->fail(BK_E_STATE, "%s: this context was created without a device (BK_DEVICE_NONE)", who);
     if (!ctx->lensmap_valid || !ctx->d_offsets) return ctx->fail(BK_E_STATE, "%s: no lensmap (bk_build / bk_set_lensmap first)", who);
@@ -880,11 +936,35 @@ extern "C" int bk_apply_rgba_fb_device(bk_ctx *ctx, const void *const plates_dev
     for (int p = 0; p < BK_MAX_PLATES; ++p)
         if (!plates_dev[p] && ctx->fp_summary(p)[0] != 0)
             return ctx->fail(BK_E_INVALID, "%s: plate %d is NULL, but the lensmap reads %d of its tiles (bk_plate_footprint)", who, p, ctx->fp_summary(p)[0]);
+    return BK_OK;
+}
+
+// one truecolour frame out of six row-major 32-bit plates in device memory: no ring slot, no block map, either apply variant
+extern "C" int bk_apply_rgba_fb_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES], void *dst_dev,
+                                       int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256], int ss2)
+{
+    static const char *who = "bk_apply_rgba_fb_device";
+    if (int r = fb_apply_args(ctx, who, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, ss2)) return r;
     bk::Range range(who);
     if (lut)
         if (int r = upload_lut_fb(ctx, lut)) return r;
     uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + (ss2 ? ctx->row0 / 2 : ctx->row0)) * dst_pitch + (size_t)x0 * 4;
     return bk::launch_apply_rgba_fb(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->d_lut_fb : nullptr, ss2 != 0);
+}
+
+// the same frame, every mapped pixel blended from the four texels around where its ray landed (the sub-texel plane of bk_set_subtexel)
+extern "C" int bk_apply_rgba_fb_bilinear_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
+                                                void *dst_dev, int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256])
+{
+    static const char *who = "bk_apply_rgba_fb_bilinear_device";
+    if (int r = fb_apply_args(ctx, who, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, 0)) return r;
+    if (!ctx->subtexel_valid || !ctx->d_subtexel)
+        return ctx->fail(BK_E_STATE, "%s: the lensmap has no sub-texel plane (bk_set_subtexel(ctx, 1), then bk_build / bk_set_lensmap)", who);
+    bk::Range range(who);
+    if (lut)
+        if (int r = upload_lut_fb(ctx, lut)) return r;
+    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
+    return bk::launch_apply_rgba_fb_bilinear(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->d_lut_fb : nullptr);
 }
 
 // ---- resident single-frame apply (bk_apply_resident.inc) ------------------------------------------------------------

@@ -295,14 +295,14 @@ __global__ __launch_bounds__(256) void scatter_kernel(T *__restrict__ dst, const
 // The reference stops building at the first malformed callback result (status -1, fisheye.c:2113-2115) and keeps what its scan -
 // rows from the bottom up, pixels left to right - had set by then.  The GPU build evaluates every pixel; this pass takes away
 // the entries the reference would not have reached (scan key <= the failing pixel's) and recounts the display flags.
-__global__ __launch_bounds__(256) void truncate_scan_kernel(uint32_t *__restrict__ off, uint8_t *__restrict__ tints, int W, int row0, size_t n,
-                                                            uint32_t bad_key, uint32_t plate_bytes, int *__restrict__ display)
+__global__ __launch_bounds__(256) void truncate_scan_kernel(uint32_t *__restrict__ off, uint8_t *__restrict__ tints, uint16_t *__restrict__ sub, int W, int row0,
+                                                            size_t n, uint32_t bad_key, uint32_t plate_bytes, int *__restrict__ display)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int lyl = (int)(i / (size_t)W), lx = (int)(i - (size_t)lyl * W), ly = row0 + lyl;
     const uint32_t key = (uint32_t)(ly * W + (W - 1 - lx)) + 1u;
-    if (key <= bad_key) { off[i] = BK_NULL_OFFSET; tints[i] = 255; return; }
+    if (key <= bad_key) { off[i] = BK_NULL_OFFSET; tints[i] = 255; if (sub) sub[i] = 0x8080; return; }      // (sub: the sub-texel plane, or null)
     const uint32_t o = off[i];
     if (o != BK_NULL_OFFSET) {
         const uint32_t plate = o / plate_bytes;
@@ -317,8 +317,8 @@ int launch_truncate_scan(bk_ctx *ctx, unsigned int bad_key, int display_out[BK_M
 {
     const size_t n = (size_t)ctx->W * ctx->rows();
     BK_HIP(ctx, hipMemsetAsync(ctx->d_display, 0, BK_MAX_PLATES * sizeof(int), ctx->stream));
-    if (n) hipLaunchKernelGGL(truncate_scan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->W,
-                              ctx->row0, n, bad_key, (uint32_t)ctx->plate_bytes(), ctx->d_display);
+    if (n) hipLaunchKernelGGL(truncate_scan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints,
+                              ctx->subtexel_valid ? ctx->d_subtexel : nullptr, ctx->W, ctx->row0, n, bad_key, (uint32_t)ctx->plate_bytes(), ctx->d_display);
     BK_HIP(ctx, hipGetLastError());
     BK_HIP(ctx, hipMemcpyAsync(display_out, ctx->d_display, BK_MAX_PLATES * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -479,5 +479,6 @@ static int scatter_impl(bk_ctx *ctx, T *dst, const uint32_t *h_idx, const T *h_v
 }
 int launch_scatter32(bk_ctx *ctx, uint32_t *dst, const uint32_t *h_idx, const uint32_t *h_val, size_t n) { return scatter_impl<uint32_t>(ctx, dst, h_idx, h_val, n); }
 int launch_scatter8(bk_ctx *ctx, uint8_t *dst, const uint32_t *h_idx, const uint8_t *h_val, size_t n) { return scatter_impl<uint8_t>(ctx, dst, h_idx, h_val, n); }
+int launch_scatter16(bk_ctx *ctx, uint16_t *dst, const uint32_t *h_idx, const uint16_t *h_val, size_t n) { return scatter_impl<uint16_t>(ctx, dst, h_idx, h_val, n); }
 
 }  // namespace bk

@@ -264,6 +264,116 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_ss2_kernel(const uint32_t *
     }
 }
 
+// ---- BILINEAR (bk_apply_rgba_fb_bilinear_device) ----------------------------------------------------------------------------------
+// The reference keeps trunc(u * ps) of a ray's position on its plate (fisheye.c:1988, after :2055-2062) and render_lensmap reads that one
+// texel; the build can keep the eight fraction bits beside it (BkBuildParams::subtexel: qx | qy << 8), and this kernel blends the four
+// texels around the position.  Texel centres sit at px + 1/2, so with sx = qx + 128 the left texel of the pair is px - 1 + (sx >> 8) and
+// the right one's weight fx = sx & 255 (of 256); rows alike.  Both are clamped to the entry's OWN plate: no filtering across a cube seam.
+// Integer and exact, per byte: h0 = a00 * (256 - fx) + a01 * fx, h1 = a10 * (256 - fx) + a11 * fx, out = (h0 * (256 - fy) + h1 * fy +
+// 32768) >> 16.  Sub 0x8080 is fx = fy = 0 on the named texel itself: the nearest kernel's frame, byte for byte.
+// Layout: apply_rgba_fb_kernel's - 128 x 8 pixels a workgroup, four consecutive pixels a lane, entries one 16-byte load, subs one
+// 8-byte load (W % 4 == 0), ONE decode per pixel (bk_fb_locate), the three neighbours the same base with clamped coordinates; all
+// sixteen addresses are formed before the first texel is used, an unmapped pixel's four are the lane's own lensmap entry.  The first
+// stage runs on even and odd bytes as two 16-bit fields a dword (a field's sum is at most 255 * 256: no carry), two 24-bit multiplies
+// each; the second per byte as (h0 << 8) + fy * (h1 - h0) - the same number - one signed 24-bit multiply.  Tinted: every one of the
+// four texels goes through bk_fb_tint first, as ss2 tints per sample before its average.
+// As built (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; no scratch): plain / tinted 49 / 66 VGPRs = 8 / 7 waves per SIMD.
+// Measured: tools/bench_rgba.py --fb --bilinear [--tint], profiles/rgba_fb_bilinear_apply.txt.
+
+// bk_fb_texel's decode with the parts handed out: the plate's base, its pitch, the texel's column and row
+__device__ __forceinline__ void bk_fb_locate(const BkFbPlates &s, const BkFbGeom &g, uint32_t off, const uint8_t *&base, uint32_t &pitch, uint32_t &px,
+                                             uint32_t &py)
+{
+    // (selects on the five comparisons, as in bk_fb_texel: picked by the plate's number the struct is copied to scratch)
+    const bool c1 = off >= g.pb, c2 = off >= 2u * g.pb, c3 = off >= 3u * g.pb, c4 = off >= 4u * g.pb, c5 = off >= 5u * g.pb;
+    const uint32_t plate = (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3 + (uint32_t)c4 + (uint32_t)c5;
+    base = c5 ? s.p[5] : c4 ? s.p[4] : c3 ? s.p[3] : c2 ? s.p[2] : c1 ? s.p[1] : s.p[0];
+    pitch = c5 ? s.pitch[5] : c4 ? s.pitch[4] : c3 ? s.pitch[3] : c2 ? s.pitch[2] : c1 ? s.pitch[1] : s.pitch[0];
+    BK_FB_TEXEL(off - plate * g.pb, g.tpr, g.tpr_m, __umulhi, px, py);
+}
+
+// the blend of one pixel: a00 a01 (upper row), a10 a11 (lower row), weights fx, fy in 0..255 of 256
+__device__ __forceinline__ uint32_t bk_fb_blend(uint32_t a00, uint32_t a01, uint32_t a10, uint32_t a11, uint32_t fx, uint32_t fy)
+{
+    const uint32_t m = 0x00FF00FFu, gx = 256u - fx;
+    // bytes 0 / 2 and bytes 1 / 3 as 16-bit fields: every operand below 2^24, every field's sum at most 65280
+    const uint32_t h0e = __umul24(a00 & m, gx) + __umul24(a01 & m, fx), h0o = __umul24((a00 >> 8) & m, gx) + __umul24((a01 >> 8) & m, fx);
+    const uint32_t h1e = __umul24(a10 & m, gx) + __umul24(a11 & m, fx), h1o = __umul24((a10 >> 8) & m, gx) + __umul24((a11 >> 8) & m, fx);
+    // h0 * (256 - fy) + h1 * fy = (h0 << 8) + fy * (h1 - h0), |h1 - h0| <= 65280: a signed 24-bit product; the sum is below 2^24 + 2^15
+#define BK_FB_STAGE2(h0, h1) ((uint32_t)((int)((h0) << 8) + __mul24((int)(h1) - (int)(h0), (int)fy) + 32768) >> 16)
+    const uint32_t b0 = BK_FB_STAGE2(h0e & 0xFFFFu, h1e & 0xFFFFu), b2 = BK_FB_STAGE2(h0e >> 16, h1e >> 16);
+    const uint32_t b1 = BK_FB_STAGE2(h0o & 0xFFFFu, h1o & 0xFFFFu), b3 = BK_FB_STAGE2(h0o >> 16, h1o >> 16);
+#undef BK_FB_STAGE2
+    return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+}
+
+// sub = the sub-texel plane, [rows][W] as lmap; ps_m1 = platesize - 1; otherwise apply_rgba_fb_kernel's arguments and grid
+template <bool RUBIX>
+__global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint32_t *__restrict__ lmap, const uint8_t *__restrict__ tints,
+                                                                     const uint16_t *__restrict__ sub, const BkFbPlates src, const BkFbGeom g, uint32_t ps_m1,
+                                                                     uint8_t *__restrict__ dst, int dst_pitch, const uint8_t *__restrict__ lut)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lut_s[RUBIX ? 4 * BK_PAL_BYTES : 16];
+    if (RUBIX) bk_fb_load_lut(lut, lut_s);
+    const int x = (int)blockIdx.x * 128 + (int)(threadIdx.x & 31u) * 4, row = (int)blockIdx.y * 8 + (int)(threadIdx.x >> 5);
+    if (row >= g.rows || x >= g.W) return;
+    uint32_t o[4], t[4], q[4];
+    bk_fb_entries<4, RUBIX>(lmap, tints, g, row, x, o, t);
+    const size_t at = (size_t)row * g.W + x;
+    if (g.lmap4) {                                   // (x + 3 < W; at % 4 == 0: eight aligned bytes)
+        const uint2 s2 = *reinterpret_cast<const uint2 *>(sub + at);
+        q[0] = s2.x & 0xFFFFu; q[1] = s2.x >> 16; q[2] = s2.y & 0xFFFFu; q[3] = s2.y >> 16;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = x + k < g.W ? (uint32_t)sub[at + k] : 0x8080u;
+    }
+    if ((o[0] & o[1] & o[2] & o[3]) == BK_NULL_OFFSET) return;
+    const uint32_t *spare = lmap + at;               // what an unmapped pixel loads instead of its texels
+    const uint32_t *a[16];
+    uint32_t fx[4], fy[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool mapped = o[k] != BK_NULL_OFFSET;
+        const uint8_t *base;
+        uint32_t pitch, px, py;
+        bk_fb_locate(src, g, o[k], base, pitch, px, py);
+        const uint32_t sx = (q[k] & 255u) + 128u, sy = (q[k] >> 8) + 128u;
+        fx[k] = sx & 255u; fy[k] = sy & 255u;
+        // the pair px - 1 + (sx >> 8), + 1, clamped to the plate: the left one can only fall below 0, the right one only pass ps - 1
+        const uint32_t xr = px + (sx >> 8), yr = py + (sy >> 8);
+        const uint32_t xa = xr ? xr - 1u : 0u, ya = yr ? yr - 1u : 0u;
+        const uint32_t xb = xr < ps_m1 ? xr : ps_m1, yb = yr < ps_m1 ? yr : ps_m1;
+        const uint8_t *ra = base + (size_t)ya * pitch, *rb = base + (size_t)yb * pitch;
+        a[4 * k] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xa * 4u) : spare;
+        a[4 * k + 1] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xb * 4u) : spare;
+        a[4 * k + 2] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xa * 4u) : spare;
+        a[4 * k + 3] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xb * 4u) : spare;
+    }
+    uint32_t w[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) w[k] = *a[k];
+    uint32_t v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (RUBIX) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[4 * k + j] = bk_fb_tint(w[4 * k + j], t[k], lut_s);
+        }
+        v[k] = bk_fb_blend(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3], fx[k], fy[k]);
+    }
+    uint8_t *out = dst + (size_t)row * dst_pitch + (size_t)x * 4;
+    const bool all = o[0] != BK_NULL_OFFSET && o[1] != BK_NULL_OFFSET && o[2] != BK_NULL_OFFSET && o[3] != BK_NULL_OFFSET;      // (entries past W are NULL)
+    if (all && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+        v4u r = {v[0], v[1], v[2], v[3]};
+        __builtin_nontemporal_store(r, reinterpret_cast<v4u *>(out));
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (o[k] != BK_NULL_OFFSET) reinterpret_cast<uint32_t *>(out)[k] = v[k];
+    }
+}
+
 // dst = pixel (x0, y0 + row0) of the frame - ss2: (x0, y0 + row0 / 2) of the half-size frame; plates / pitches: validated by the
 // caller (a NULL plate is one no entry of the owned rows names); d_lut != nullptr: the tinted launch
 int launch_apply_rgba_fb(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
@@ -292,6 +402,32 @@ int launch_apply_rgba_fb(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], c
         if (d_lut) hipLaunchKernelGGL(apply_rgba_fb_kernel<true>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, src, g, dst, dst_pitch, d_lut);
         else hipLaunchKernelGGL(apply_rgba_fb_kernel<false>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, src, g, dst, dst_pitch, d_lut);
     }
+    BK_HIP(ctx, hipGetLastError());
+    return BK_OK;
+}
+
+// dst = pixel (x0, y0 + row0) of the frame; the caller has made sure of the sub-texel plane
+int launch_apply_rgba_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
+                                  const uint8_t *d_lut)
+{
+    const int rows = ctx->rows();
+    if (rows <= 0 || ctx->W <= 0) return BK_OK;
+    BkFbPlates src;
+    for (int p = 0; p < BK_MAX_PLATES; ++p) {
+        src.p[p] = (const uint8_t *)plates[p];
+        src.pitch[p] = plates[p] ? (uint32_t)pitches[p] : 0u;
+    }
+    BkFbGeom g;
+    g.pb = (uint32_t)ctx->gp * (uint32_t)ctx->ph;
+    g.tpr = (uint32_t)ctx->gp >> 4;
+    g.tpr_m = bk_fb_recip(g.tpr);
+    g.W = ctx->W;
+    g.rows = rows;
+    g.lmap4 = (ctx->W & 3) == 0;
+    const uint32_t ps_m1 = (uint32_t)ctx->ps - 1u;
+    const dim3 grid((unsigned)((ctx->W + 127) / 128), (unsigned)((rows + 7) / 8));
+    if (d_lut) hipLaunchKernelGGL(apply_rgba_fb_bilinear_kernel<true>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut);
+    else hipLaunchKernelGGL(apply_rgba_fb_bilinear_kernel<false>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut);
     BK_HIP(ctx, hipGetLastError());
     return BK_OK;
 }

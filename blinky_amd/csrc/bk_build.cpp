@@ -54,6 +54,7 @@ static void fill_params(bk_ctx *ctx, BkBuildParams *bp)
     }
     bp->offsets = ctx->d_offsets;
     bp->tints = ctx->d_tints;
+    bp->subtexel = ctx->d_subtexel;               // (null unless bk_set_subtexel is on: the kernel then stores nothing)
     bp->display = ctx->d_display;
     bp->err = ctx->d_display + BK_MAX_PLATES;
     bp->flag_count = (unsigned int *)(ctx->d_display + BK_MAX_PLATES + 1);
@@ -116,11 +117,12 @@ bool h_offgrid(const BkBuildParams &bp, int px, int py)                         
     return !(__builtin_fmod(ux, bp.rubix_block) < bp.rubix_pad || __builtin_fmod(uy, bp.rubix_block) < bp.rubix_pad);
 }
 
-/* one pixel of resume_lensmap_inverse (fisheye.c:2084-2124, 1545-1588, 1995-2013); o = index inside the owned stripe */
-void h_inverse_entry(HostEval &E, const BkBuildParams &bp, uint32_t o, uint32_t *off, uint8_t *tint,
+/* one pixel of resume_lensmap_inverse (fisheye.c:2084-2124, 1545-1588, 1995-2013); o = index inside the owned stripe; *sub = where inside
+ * the texel the ray landed (what :1988 drops; bk_inverse_entry's three lines), 0x8080 for an entry that names none */
+void h_inverse_entry(HostEval &E, const BkBuildParams &bp, uint32_t o, uint32_t *off, uint8_t *tint, uint16_t *sub,
                      int *plate_shown, int *err)
 {
-    *off = BK_NULL_OFFSET; *tint = 255; *plate_shown = -1;
+    *off = BK_NULL_OFFSET; *tint = 255; *sub = 0x8080; *plate_shown = -1;
     const int lyl = (int)(o / (uint32_t)bp.W), lx = (int)(o - (uint32_t)lyl * (uint32_t)bp.W), ly = bp.row0 + lyl;
     const double y = (double)(-(ly - bp.H / 2)) * bp.scale, x = (double)(lx - bp.W / 2) * bp.scale;
     Values r = E.call(E.lens_inverse, Values{Value::number(x), Value::number(y)});
@@ -133,11 +135,13 @@ void h_inverse_entry(HostEval &E, const BkBuildParams &bp, uint32_t o, uint32_t 
         const double px_ = (double)h_dot3(p.right, ray), py_ = (double)h_dot3(p.up, ray), pz_ = (double)h_dot3(p.forward, ray);
         const double u = px_ / pz_ * p.dist64 + 0.5, v = -py_ / pz_ * p.dist64 + 0.5;
         if (u >= 0 && u <= 1 && v >= 0 && v <= 1) {
-            const int px = h_trunc_to_int(u * bp.ps), py = h_trunc_to_int(v * bp.ps);
+            const double us = u * bp.ps, vs = v * bp.ps;
+            const int px = h_trunc_to_int(us), py = h_trunc_to_int(vs);
             if (px >= 0 && px < bp.ps && py >= 0 && py < bp.ps) {
                 *plate_shown = plate;
                 *off = bk_texel_offset((unsigned)bp.gp, (unsigned)bp.ph, (unsigned)plate, (unsigned)px, (unsigned)py);
                 if (h_offgrid(bp, px, py)) *tint = (uint8_t)plate;
+                *sub = (uint16_t)((int)((us - (double)px) * 256.0) | (int)((vs - (double)py) * 256.0) << 8);      /* exact: 0 <= us - px < 1 */
             }
         }
     } else if (!(r.size() == 1 && r[0].t == Value::NIL)) {
@@ -345,13 +349,18 @@ static int patch_changed(bk_ctx *ctx, const std::vector<uint32_t> &flagged, cons
 }
 
 /* Where a host-built table goes: into the context's device lensmap - or, for bk_debug_host_build on a context without a device, into the
- * caller's arrays (ctx->host_sink_*).  `off` == nullptr: the empty table. */
-static int deliver_host_table(bk_ctx *ctx, const uint32_t *off, const uint8_t *tint)
+ * caller's arrays (ctx->host_sink_*).  `off` == nullptr: the empty table.  `sub` == nullptr: every entry at its texel's centre (a forward
+ * build, the empty table); it goes wherever a sub-texel plane is kept (bk_set_subtexel, bk_debug_host_build_subtexel). */
+static int deliver_host_table(bk_ctx *ctx, const uint32_t *off, const uint8_t *tint, const uint16_t *sub)
 {
     const size_t px = (size_t)ctx->W * ctx->rows();
     if (ctx->host_sink_off) {
         if (off) { memcpy(ctx->host_sink_off, off, px * 4); memcpy(ctx->host_sink_tint, tint, px); }
         else { memset(ctx->host_sink_off, 0xFF, px * 4); memset(ctx->host_sink_tint, 255, px); }
+        if (ctx->host_sink_sub) {
+            if (off && sub) memcpy(ctx->host_sink_sub, sub, px * 2);
+            else memset(ctx->host_sink_sub, 0x80, px * 2);
+        }
         return BK_OK;
     }
     if (off) {
@@ -360,6 +369,10 @@ static int deliver_host_table(bk_ctx *ctx, const uint32_t *off, const uint8_t *t
     } else {
         BK_HIP(ctx, hipMemsetAsync(ctx->d_offsets, 0xFF, px * 4, ctx->stream));
         BK_HIP(ctx, hipMemsetAsync(ctx->d_tints, 255, px, ctx->stream));
+    }
+    if (ctx->d_subtexel) {
+        if (off && sub) BK_HIP(ctx, hipMemcpyAsync(ctx->d_subtexel, sub, px * 2, hipMemcpyHostToDevice, ctx->stream));
+        else BK_HIP(ctx, hipMemsetAsync(ctx->d_subtexel, 0x80, px * 2, ctx->stream));
     }
     BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return BK_OK;
@@ -375,6 +388,7 @@ static int build_sequential(bk_ctx *ctx, LensProgram *P, const std::string &sour
     const size_t px = (size_t)ctx->W * ctx->rows();
     std::vector<uint32_t> off(px, BK_NULL_OFFSET);
     std::vector<uint8_t> tint(px, 255);
+    std::vector<uint16_t> sub(px, (uint16_t)0x8080);
     int disp[BK_MAX_PLATES] = {0, 0, 0, 0, 0, 0};
     int errbits = 0;
     const auto t0 = std::chrono::steady_clock::now();
@@ -382,7 +396,7 @@ static int build_sequential(bk_ctx *ctx, LensProgram *P, const std::string &sour
     HostModuleP hm = !source.empty() && P->interp.math == &math_platform() && bk::g_debug.host_module != 2 ? host_module_for(source, true) : nullptr;
     ctx->last_fixup_compiled = hm != nullptr;
     try {
-        if (hm) errbits = hm->inverse_scan(&bp, off.data(), tint.data(), disp);
+        if (hm) errbits = hm->inverse_scan(&bp, off.data(), tint.data(), sub.data(), disp);
         else {
             const Values roots_in{P->lens_inverse, P->lens_forward, P->globe_plate};
             Values roots;
@@ -392,9 +406,9 @@ static int build_sequential(bk_ctx *ctx, LensProgram *P, const std::string &sour
                 for (int lx = 0; lx < ctx->W && !errbits; ++lx) {
                     const size_t o = (size_t)lyl * ctx->W + lx;
                     int shown = -1;
-                    h_inverse_entry(ev, bp, (uint32_t)o, &off[o], &tint[o], &shown, &errbits);
+                    h_inverse_entry(ev, bp, (uint32_t)o, &off[o], &tint[o], &sub[o], &shown, &errbits);
                     if (errbits) {
-                        off[o] = BK_NULL_OFFSET; tint[o] = 255;
+                        off[o] = BK_NULL_OFFSET; tint[o] = 255; sub[o] = 0x8080;
                         if (errbits == BK_ERR_RESULT) ctx->last_bad_key = (uint32_t)(((uint32_t)ctx->row0 + (uint32_t)lyl) * (uint32_t)ctx->W + ((uint32_t)ctx->W - 1u - (uint32_t)lx)) + 1u;
                     }
                     else if (shown >= 0) disp[shown] = 1;
@@ -409,9 +423,10 @@ static int build_sequential(bk_ctx *ctx, LensProgram *P, const std::string &sour
     if (errbits & ~BK_ERR_RESULT) {                              // a Lua runtime error: nothing is drawn (see bk_build)
         std::fill(off.begin(), off.end(), BK_NULL_OFFSET);
         std::fill(tint.begin(), tint.end(), (uint8_t)255);
+        std::fill(sub.begin(), sub.end(), (uint16_t)0x8080);
         for (int &d : disp) d = 0;
     }
-    if (int r = deliver_host_table(ctx, off.data(), tint.data())) return r;
+    if (int r = deliver_host_table(ctx, off.data(), tint.data(), sub.data())) return r;
     for (int i = 0; i < BK_MAX_PLATES; ++i) { ctx->display[i] = i < ctx->numplates ? disp[i] : 0; if (display_out) display_out[i] = ctx->display[i]; }
     if (errbits) return ctx->fail(BK_E_SCRIPT, "lensmap build: %s", err_text(errbits));
     return BK_OK;
@@ -489,20 +504,20 @@ void h_draw_quad(const HostTable &T, const int *tl, const int *tr, const int *bl
 }  // namespace
 
 /* what a host build leaves in the context: the table on the device, display flags, timings, and how it was built */
-static int finish_host_build(bk_ctx *ctx, const std::vector<uint32_t> &off, const std::vector<uint8_t> &tint, const int disp[BK_MAX_PLATES],
-                             int display_out[BK_MAX_PLATES], std::chrono::steady_clock::time_point t0)
+static int finish_host_build(bk_ctx *ctx, const std::vector<uint32_t> &off, const std::vector<uint8_t> &tint, const uint16_t *sub /* null: all centre */,
+                             const int disp[BK_MAX_PLATES], int display_out[BK_MAX_PLATES], std::chrono::steady_clock::time_point t0)
 {
     ctx->last_host_eval_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ctx->last_build_ms = ctx->last_host_eval_ms;
     ctx->last_flagged = ctx->last_changed = 0;
-    if (int r = deliver_host_table(ctx, off.data(), tint.data())) return r;
+    if (int r = deliver_host_table(ctx, off.data(), tint.data(), sub)) return r;
     for (int i = 0; i < BK_MAX_PLATES; ++i) { ctx->display[i] = i < ctx->numplates ? disp[i] : 0; if (display_out) display_out[i] = ctx->display[i]; }
     return BK_OK;
 }
 static int empty_host_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], const char *what)
 {
     // a Lua run-time error, which the reference's unprotected lua_call does not survive: nothing is drawn (see bk_build)
-    if (int r = deliver_host_table(ctx, nullptr, nullptr)) return r;
+    if (int r = deliver_host_table(ctx, nullptr, nullptr, nullptr)) return r;
     for (int i = 0; i < BK_MAX_PLATES; ++i) { ctx->display[i] = 0; if (display_out) display_out[i] = 0; }
     return ctx->fail(BK_E_SCRIPT, "lensmap build: %s", what);
 }
@@ -515,6 +530,7 @@ static int build_inverse_pool(bk_ctx *ctx, LensProgram *P, const BkBuildParams &
     const size_t px = (size_t)ctx->W * ctx->rows();
     std::vector<uint32_t> off(px, BK_NULL_OFFSET);
     std::vector<uint8_t> tint(px, 255);
+    std::vector<uint16_t> sub(px, (uint16_t)0x8080);
     std::vector<int8_t> shown(px, (int8_t)-1);
     std::vector<uint8_t> err(px, 0);
     int disp[BK_MAX_PLATES] = {0, 0, 0, 0, 0, 0};
@@ -522,7 +538,7 @@ static int build_inverse_pool(bk_ctx *ctx, LensProgram *P, const BkBuildParams &
     try {
         for_each_flagged(P, px, [&](HostEval &E, size_t o) {
             int s = -1, e = 0;
-            h_inverse_entry(E, bp, (uint32_t)o, &off[o], &tint[o], &s, &e);
+            h_inverse_entry(E, bp, (uint32_t)o, &off[o], &tint[o], &sub[o], &s, &e);
             shown[o] = (int8_t)s; err[o] = (uint8_t)e;
         });
     } catch (const LuaError &e) {
@@ -540,12 +556,12 @@ static int build_inverse_pool(bk_ctx *ctx, LensProgram *P, const BkBuildParams &
         for (size_t o = 0; o < px; ++o) {
             const uint32_t lyl = (uint32_t)(o / (size_t)ctx->W), lx = (uint32_t)(o - (size_t)lyl * ctx->W);
             const uint32_t key = (uint32_t)(((uint32_t)ctx->row0 + lyl) * (uint32_t)ctx->W + ((uint32_t)ctx->W - 1u - lx)) + 1u;
-            if (key <= bad_key) { off[o] = BK_NULL_OFFSET; tint[o] = 255; shown[o] = -1; }
+            if (key <= bad_key) { off[o] = BK_NULL_OFFSET; tint[o] = 255; sub[o] = 0x8080; shown[o] = -1; }
         }
     }
     for (size_t o = 0; o < px; ++o) if (shown[o] >= 0) disp[shown[o]] = 1;
     ctx->last_bad_key = bad_key;
-    if (int r = finish_host_build(ctx, off, tint, disp, display_out, t0)) return r;
+    if (int r = finish_host_build(ctx, off, tint, sub.data(), disp, display_out, t0)) return r;
     if (bad_key) return ctx->fail(BK_E_SCRIPT, "lensmap build: %s", err_text(BK_ERR_RESULT));
     return BK_OK;
 }
@@ -614,7 +630,7 @@ static int build_forward_host(bk_ctx *ctx, LensProgram *P, const BkBuildParams &
         return empty_host_build(ctx, display_out, e.what());
     }
     if (errbits) return empty_host_build(ctx, display_out, err_text(errbits));
-    return finish_host_build(ctx, off, tint, disp, display_out, t0);
+    return finish_host_build(ctx, off, tint, nullptr, disp, display_out, t0);      // (the quad rasteriser has no per-pixel uv: every entry at its texel's centre)
 }
 
 /* bk_build for a script the emitter declined (`why` = its refusal) */
@@ -653,7 +669,8 @@ extern "C" int bk_last_build_path(const bk_ctx *ctx, char *why, size_t cap)
  * mode 1 = the worker pool, 2 = one sequential scan, 0 = whichever bk_build would take for a script the emitter declines.  The table
  * comes back in the reference's layout (plate * ps * ps + py * ps + px, 0xFFFFFFFF = NULL); display_out as bk_build's; the return value
  * is bk_build's (BK_E_SCRIPT with the truncated / empty table in place).  Inverse maps never use the compiled host module here. */
-extern "C" int bk_debug_host_build(bk_ctx *ctx, int mode, uint32_t *offsets, uint8_t *tints, int display_out[BK_MAX_PLATES], double *scale_out)
+static int debug_host_build(bk_ctx *ctx, int mode, uint32_t *offsets, uint8_t *tints, uint16_t *sub /* nullable */, int display_out[BK_MAX_PLATES],
+                            double *scale_out)
 {
     if (!ctx || !offsets || !tints || mode < 0 || mode > 2) return BK_E_INVALID;
     LensProgram *P = ctx->prog;
@@ -663,13 +680,14 @@ extern "C" int bk_debug_host_build(bk_ctx *ctx, int mode, uint32_t *offsets, uin
     const size_t px = (size_t)ctx->W * ctx->rows();
     memset(offsets, 0xFF, px * 4);
     memset(tints, 255, px);
+    if (sub) memset(sub, 0x80, px * 2);
     for (int i = 0; i < BK_MAX_PLATES; ++i) { ctx->display[i] = 0; if (display_out) display_out[i] = 0; }
     ctx->last_bad_key = 0;
     if (int r = bk_calc_zoom(ctx, scale_out)) return r;
     if (P->info.map_type == BK_MAP_NONE) return ctx->fail(BK_E_STATE, "no inverse or forward map being used");
     BkBuildParams bp;
     fill_params(ctx, &bp);
-    ctx->host_sink_off = offsets; ctx->host_sink_tint = tints;
+    ctx->host_sink_off = offsets; ctx->host_sink_tint = tints; ctx->host_sink_sub = sub;
     int rc;
     if (mode == 0) rc = build_on_host(ctx, P, "bk_debug_host_build", display_out);
     else if (P->info.map_type == BK_MAP_INVERSE) {
@@ -679,7 +697,7 @@ extern "C" int bk_debug_host_build(bk_ctx *ctx, int mode, uint32_t *offsets, uin
         if (!P->lens_forward.is_function()) rc = ctx->fail(BK_E_STATE, "lens has no lens_forward");
         else rc = build_forward_host(ctx, P, bp, mode == 2, display_out);
     }
-    ctx->host_sink_off = nullptr; ctx->host_sink_tint = nullptr;
+    ctx->host_sink_off = nullptr; ctx->host_sink_tint = nullptr; ctx->host_sink_sub = nullptr;
     for (size_t i = 0; i < px; ++i) {
         if (offsets[i] == BK_NULL_OFFSET) continue;
         unsigned plate, x, y;
@@ -687,6 +705,18 @@ extern "C" int bk_debug_host_build(bk_ctx *ctx, int mode, uint32_t *offsets, uin
         offsets[i] = plate * (unsigned)(ctx->ps * ctx->ps) + y * (unsigned)ctx->ps + x;
     }
     return rc;
+}
+extern "C" int bk_debug_host_build(bk_ctx *ctx, int mode, uint32_t *offsets, uint8_t *tints, int display_out[BK_MAX_PLATES], double *scale_out)
+{
+    return debug_host_build(ctx, mode, offsets, tints, nullptr, display_out, scale_out);
+}
+/* ... with the sub-texel plane the same build keeps under bk_set_subtexel (uint16 [rows][W]: qx | qy << 8, 0x8080 where the entry has no
+ * position of its own - NULL entries, every entry of a forward map); the context's switch plays no part */
+extern "C" int bk_debug_host_build_subtexel(bk_ctx *ctx, int mode, uint32_t *offsets, uint8_t *tints, uint16_t *sub, int display_out[BK_MAX_PLATES],
+                                            double *scale_out)
+{
+    if (!sub) return BK_E_INVALID;
+    return debug_host_build(ctx, mode, offsets, tints, sub, display_out, scale_out);
 }
 #endif
 
@@ -736,10 +766,11 @@ static int build_inverse_device(bk_ctx *ctx, LensProgram *P, const std::string &
     const size_t nfl = flagged.size() / 4;
     std::vector<uint32_t> roff(nfl);
     std::vector<uint8_t> rtint(nfl);
+    std::vector<uint16_t> rsub(nfl);
     std::vector<int> rshown(nfl), rerr(nfl, 0);
     rederive(ctx, P, src, flagged.data(), 4, nfl, true,
-             [&](const HostModule &hm, const uint32_t *id, int stride, unsigned long cnt, size_t i) { hm.inverse(&bp, id, stride, cnt, &roff[i], &rtint[i], &rshown[i], &rerr[i]); },
-             [&](HostEval &E, uint32_t id, size_t i) { h_inverse_entry(E, bp, id, &roff[i], &rtint[i], &rshown[i], &rerr[i]); });
+             [&](const HostModule &hm, const uint32_t *id, int stride, unsigned long cnt, size_t i) { hm.inverse(&bp, id, stride, cnt, &roff[i], &rtint[i], &rsub[i], &rshown[i], &rerr[i]); },
+             [&](HostEval &E, uint32_t id, size_t i) { h_inverse_entry(E, bp, id, &roff[i], &rtint[i], &rsub[i], &rshown[i], &rerr[i]); });
     unsigned int bad_key = (unsigned)counters[BK_MAX_PLATES + 2];
     for (size_t i = 0; i < nfl; ++i) {
         counters[BK_MAX_PLATES] |= rerr[i];
@@ -751,6 +782,16 @@ static int build_inverse_device(bk_ctx *ctx, LensProgram *P, const std::string &
     }
     counters[BK_MAX_PLATES + 2] = (int)bad_key;
     if (int r = patch_changed(ctx, flagged, {roff.data()}, rtint.data(), ctx->d_offsets, ctx->d_tints)) return r;
+    // the sub-texel plane of the flagged entries: a ray component narrowed to the neighbouring float moves u by an ulp - the offset may
+    // stay and the sub still differ - so it is compared and patched on its own (the record's fourth word is the device's); last_changed
+    // keeps counting offsets and tints only
+    if (bp.subtexel) {
+        std::vector<uint32_t> is;
+        std::vector<uint16_t> vs;
+        for (size_t i = 0; i < nfl; ++i)
+            if (rsub[i] != (uint16_t)flagged[4 * i + 3]) { is.push_back(flagged[4 * i]); vs.push_back(rsub[i]); }
+        if (int r = bk::launch_scatter16(ctx, bp.subtexel, is.data(), vs.data(), is.size())) return r;
+    }
     BK_HIP(ctx, hipEventRecord(ctx->build_time_ev[1], ctx->stream));
     return BK_OK;
 }
@@ -942,17 +983,25 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
     LensProgram *P = ctx->prog;
     if (bk::build_module_ready(ctx) == BK_PENDING) return BK_PENDING;
     const size_t px = (size_t)ctx->W * ctx->rows();
+    if (int r = bk::subtexel_alloc(ctx)) return r;    // (bk_set_subtexel: from here on the plane follows the lensmap, on every way out)
     // F_RenderView clears the maps before (re)building, fisheye.c:731-732; whatever fails below,
     // the lensmap stays valid-and-empty so that bk_apply draws nothing, as the reference does.
     // (the device passes write every entry of the owned rows, so the clearing - 41 MB at 4K - is left to the ways out that have not
     //  filled the table: `empty_unless_built`; the host paths are handed a cleared table up front, as before)
     struct EmptyUnlessBuilt {
         bk_ctx *ctx; size_t px; bool armed = true;
-        void now() { if (armed) { (void)hipMemsetAsync(ctx->d_offsets, 0xFF, px * 4, ctx->stream); (void)hipMemsetAsync(ctx->d_tints, 255, px, ctx->stream); armed = false; } }
+        void now()
+        {
+            if (!armed) return;
+            (void)hipMemsetAsync(ctx->d_offsets, 0xFF, px * 4, ctx->stream); (void)hipMemsetAsync(ctx->d_tints, 255, px, ctx->stream);
+            if (ctx->d_subtexel) (void)hipMemsetAsync(ctx->d_subtexel, 0x80, px * 2, ctx->stream);      // (0x8080: every entry at its texel's centre)
+            armed = false;
+        }
         ~EmptyUnlessBuilt() { now(); }
     } empty_unless_built{ctx, px};
     BK_HIP(ctx, hipMemsetAsync(ctx->d_display, 0, 2 * kNumCounters * sizeof(int), ctx->stream));      // (two sets of counters: see the forward build)
     ctx->lensmap_valid = true;
+    ctx->subtexel_valid = ctx->d_subtexel != nullptr;
     ctx->last_bad_key = 0;
     ctx->spans_valid = false;
     bk::coopmap_invalidate(ctx);
@@ -1016,6 +1065,8 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
     int counters[kNumCounters];
     try {
         const bool inverse = P->info.map_type == BK_MAP_INVERSE;
+        // (the forward passes know texels, not where in them a pixel's ray lands: the plane is all centres)
+        if (!inverse && ctx->d_subtexel) BK_HIP(ctx, hipMemsetAsync(ctx->d_subtexel, 0x80, px * 2, ctx->stream));
         if (int r = inverse ? build_inverse_device(ctx, P, src, bp, counters) : build_forward_device(ctx, P, src, bp, counters)) return r;
     } catch (const LuaError &e) {
         return ctx->fail(BK_E_SCRIPT, "lensmap build: %s", e.what());
@@ -1124,14 +1175,15 @@ extern "C" int bk_debug_host_entries(bk_ctx *ctx, const uint32_t *ids, size_t n,
     const size_t px = (size_t)ctx->W * ctx->rows();
     for (size_t i = 0; i < n; ++i) if (ids[i] >= px) return ctx->fail(BK_E_INVALID, "bk_debug_host_entries: index out of range");
     std::vector<int> shown(n), err(n, 0);
+    std::vector<uint16_t> sub(n);                         // (not handed out)
     try {
         std::string src;                                  // (none: the interpreter answers)
         if (bk::g_debug.host_module != 2 && generate_source(ctx, P, &src) != BK_OK) src.clear();
         if (bk::g_debug.host_module == 1 && (src.empty() || !fixup_module(P, src)))
             return ctx->fail(BK_E_STATE, "bk_debug_host_entries: no host module (no C++ compiler, or host math is not the platform libm)");
         rederive(ctx, P, src, ids, 1, n, false,
-                 [&](const HostModule &hm, const uint32_t *id, int stride, unsigned long cnt, size_t i) { hm.inverse(&bp, id, stride, cnt, &offsets[i], &tints[i], &shown[i], &err[i]); },
-                 [&](HostEval &E, uint32_t id, size_t i) { h_inverse_entry(E, bp, id, &offsets[i], &tints[i], &shown[i], &err[i]); });
+                 [&](const HostModule &hm, const uint32_t *id, int stride, unsigned long cnt, size_t i) { hm.inverse(&bp, id, stride, cnt, &offsets[i], &tints[i], &sub[i], &shown[i], &err[i]); },
+                 [&](HostEval &E, uint32_t id, size_t i) { h_inverse_entry(E, bp, id, &offsets[i], &tints[i], &sub[i], &shown[i], &err[i]); });
     } catch (const LuaError &e) {
         return ctx->fail(BK_E_SCRIPT, "%s", e.what());
     }

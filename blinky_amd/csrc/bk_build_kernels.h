@@ -104,11 +104,15 @@ __device__ __forceinline__ void bk_publish_flags(const int *s_disp, int *display
 #ifdef BK_HAS_INVERSE
 /* one pixel of resume_lensmap_inverse + LUAtoC_lens_inverse + set_lensmap_from_ray (fisheye.c:2084-2124, 1545-1588, 1995-2013):
  * the lensmap entry of screen pixel (lx, ly) and the plate it shows (-1: none).  Shared by the build kernel and - compiled for
- * the host against the platform libm - by the re-derivation of the flagged pixels (bk_hostmod_driver.inc). */
-BK_DEV void bk_inverse_entry(const BkBuildParams &P, BkState &S, int lx, int ly, unsigned int *off_out, unsigned char *tint_out, int *plate_out)
+ * the host against the platform libm - by the re-derivation of the flagged pixels (bk_hostmod_driver.inc).
+ * sub_out (nullable: nobody keeps it): where inside the texel the ray landed (BkBuildParams::subtexel) - what :1988's conversion to int
+ * drops; 0x8080 = the centre for an entry that names no texel. */
+BK_DEV void bk_inverse_entry(const BkBuildParams &P, BkState &S, int lx, int ly, unsigned int *off_out, unsigned char *tint_out, int *plate_out,
+                             unsigned short *sub_out)
 {
     unsigned int off = 0xFFFFFFFFu;
     unsigned char tint = 255;
+    unsigned short sub = 0x8080;
     int shown = -1;
     const double y = (double)(-(ly - P.H / 2)) * P.scale;     /* :2100, integer H/2 */
     const double x = (double)(lx - P.W / 2) * P.scale;        /* :2105 */
@@ -128,12 +132,15 @@ BK_DEV void bk_inverse_entry(const BkBuildParams &P, BkState &S, int lx, int ly,
             const double u = px_ / pz_ * p.dist64 + 0.5;                 /* :2061 */
             const double v = -py_ / pz_ * p.dist64 + 0.5;                /* :2062 */
             if (u >= 0 && u <= 1 && v >= 0 && v <= 1) {                  /* :2065 */
-                const int px = bk_trunc_to_int(u * P.ps);                /* :1988 */
-                const int py = bk_trunc_to_int(v * P.ps);
+                const double us = u * P.ps, vs = v * P.ps;
+                const int px = bk_trunc_to_int(us);                      /* :1988 */
+                const int py = bk_trunc_to_int(vs);
                 if (px >= 0 && px < P.ps && py >= 0 && py < P.ps) {      /* :1971 */
                     shown = plate;                                       /* :1976 */
                     off = bk_padded_offset(P, plate, px, py);            /* :1979 */
                     if (bk_offgrid(P, px, py)) tint = (unsigned char)plate;   /* :1959 */
+                    /* the fraction :1988 drops, to eight bits: us - px is exact (0 <= us - px < 1), times 256 is exact, 0..255 */
+                    if (sub_out) sub = (unsigned short)((int)((us - (double)px) * 256.0) | (int)((vs - (double)py) * 256.0) << 8);
                 }
             }
         }
@@ -143,6 +150,7 @@ BK_DEV void bk_inverse_entry(const BkBuildParams &P, BkState &S, int lx, int ly,
     *off_out = off;
     *tint_out = tint;
     *plate_out = shown;
+    if (sub_out) *sub_out = sub;
 }
 
 #ifndef BK_HOST_MODULE
@@ -158,21 +166,23 @@ extern "C" __global__ __launch_bounds__(256) void bk_build_inverse(BkBuildParams
     bool flagged = false;
     unsigned int off = 0xFFFFFFFFu;
     unsigned char tint = 255;
+    unsigned short sub = 0x8080;
     const size_t o = (size_t)lyl * P.W + lx;
     if (lx < P.W) {
         int plate;
         BkState S;
         bk_state_init(S, &P);
-        bk_inverse_entry(P, S, lx, ly, &off, &tint, &plate);
+        bk_inverse_entry(P, S, lx, ly, &off, &tint, &plate, P.subtexel ? &sub : nullptr);      /* (uniform: the plane is kept or it is not) */
         if (plate >= 0 && !S.flag) s_disp[plate] = 1;    /* (a flagged pixel's plate is the host's to say) */
         err = S.err;
         P.offsets[o] = off;
         P.tints[o] = tint;
+        if (P.subtexel) P.subtexel[o] = sub;
         flagged = S.flag != 0;
         /* status -1 (fisheye.c:2113-2115) ends the reference's scan there: remember the first such pixel in ITS order */
         if ((err & BK_ERR_RESULT) && P.first_bad) atomicMax(P.first_bad, (unsigned int)(ly * P.W + (P.W - 1 - lx)) + 1u);
     }
-    bk_push_flagged_wave(P, flagged, (unsigned int)o, off, tint, 0u);
+    bk_push_flagged_wave(P, flagged, (unsigned int)o, off, tint, sub);
     __syncthreads();
     bk_publish_flags(s_disp, P.display, err, P.err);
 }

@@ -35,7 +35,7 @@ typedef struct {
     unsigned char *corner_ok;/* [numplates][ps+1][ps+1] */
     /* pixels / corners / texels whose discrete outcome depends on libm's last bits (bk_device_rt.h): their
      * indices are appended here and re-evaluated by the host interpreter on the platform libm */
-    unsigned int *flag_list; /* [flag_cap][4]: id, then what the device derived (offset, tint, 0 | sx, sy, ok | own, 0, 0) */
+    unsigned int *flag_list; /* [flag_cap][4]: id, then what the device derived (offset, tint, sub-texel position | sx, sy, ok | own, 0, 0) */
     unsigned int *flag_count;/* [1] total flagged (may exceed flag_cap: the host then retries with a larger list) */
     unsigned int flag_cap;
     /* forward build, second pass only: host-decided answers to "does this texel's ray select its own plate" for the
@@ -54,6 +54,10 @@ typedef struct {
     const unsigned char *tile_own;
     int *counters_out;       /* forward build, resolve pass: where to leave a copy of the 2 x 9 counters at display[] (pinned host memory), or null */
     double inv_scale_up;     /* >= 1 / scale: turns an error bound in lens units into screen pixels without a division */
+    /* inverse build, bk_set_subtexel: [rows][W] where inside its texel every mapped pixel's ray landed - qx | qy << 8, each the first
+     * eight fraction bits of u * ps / v * ps (fisheye.c:1988 keeps the integer part only); 0x8080, the texel's centre, for NULL entries.
+     * null (the default): the plane is not kept and the kernel stores nothing.  (In front of first_bad, which stays the last member.) */
+    unsigned short *subtexel;
     /* inverse build: 1 + scan key of the FIRST pixel (in the reference's scan order: rows bottom-up, pixels left to right,
      * fisheye.c:2093-2103) whose callback returned a malformed result - key = ly * W + (W - 1 - lx), max-reduced; 0 = none */
     unsigned int *first_bad;

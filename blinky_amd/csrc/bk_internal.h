@@ -94,6 +94,11 @@ struct bk_ctx {
     uint32_t *d_offsets = nullptr;   // [row1-row0][W]  offsets into the PADDED globe layout
     uint32_t *d_convert = nullptr;   // [row1-row0][W]  scratch for layout conversion at the ABI boundary
     uint8_t *d_tints = nullptr;      // [row1-row0][W]
+    // bk_set_subtexel: [row1-row0][W] where inside its texel each mapped pixel's ray landed (qx | qy << 8, 0x8080 = centre; BkBuildParams::subtexel).
+    // Allocated by the first bk_build / bk_set_lensmap / bk_set_lensmap_subtexel with the switch on, freed with the maps or by switching off;
+    // subtexel_valid: it describes the lensmap in place (lives and dies with lensmap_valid)
+    uint16_t *d_subtexel = nullptr;
+    bool subtexel_on = false, subtexel_valid = false;
     uint8_t *d_frame = nullptr;      // [row1-row0][W] staging for bk_apply (host dst)
     uint8_t *d_pal = nullptr;        // [6][256]
     uint8_t *d_lut_rgba = nullptr;   // [4][6][256] the byte LUTs of bk_apply_rgba_tinted_device; a buffer of its own (d_pal stays the 8-bit palette), allocated on first use
@@ -178,6 +183,7 @@ struct bk_ctx {
     int last_kernel_retries = 0;     // kernel re-runs because the flag list had to grow
     bool last_fixup_compiled = false;   // the flagged entries were re-derived by the compiled host module (not the interpreter)
     uint32_t *host_sink_off = nullptr; uint8_t *host_sink_tint = nullptr;   // bk_debug_host_build: a host-built table goes here instead of the device
+    uint16_t *host_sink_sub = nullptr;                                      // ... and its sub-texel plane (bk_debug_host_build_subtexel; nullable)
     int last_build_path = 0;         // of the last bk_build: 0 = GPU kernels, 1 = host worker pool, 2 = one sequential host scan (bk_last_build_path)
     std::string last_build_why;
     int sequential_build = 1;        // bk_set_sequential_build: 0 never, 1 (default) when the callbacks carry state from pixel to pixel, 2 always
@@ -222,11 +228,14 @@ int launch_plate_rgba_retile(bk_ctx *ctx, uint8_t *plane0, const uint8_t *src_de
 // the lensmap's footprint (bk_ctx::d_fp_bits / h_fp) if it is not the current one: mark, reduce, ONE host synchronisation
 int launch_footprint(bk_ctx *ctx);
 inline void footprint_invalidate(bk_ctx *ctx) { ctx->footprint_valid = false; }      // wherever the lensmap or the owned rows change
+// the sub-texel plane for the current owned rows, allocated if the switch is on and it is not there yet (bk_api.cpp)
+int subtexel_alloc(bk_ctx *ctx);
 void footprint_free(bk_ctx *ctx);
 // launch_plate_rgba_retile for the tiles of `plate` in the footprint only (which must be current and not empty for that plate)
 int launch_plate_rgba_retile_footprint(bk_ctx *ctx, int plate, uint8_t *plane0, const uint8_t *src_dev, size_t src_pitch);
 int launch_scatter32(bk_ctx *ctx, uint32_t *dst, const uint32_t *h_idx, const uint32_t *h_val, size_t n);   // dst[idx[i]] = val[i]; synchronous
 int launch_scatter8(bk_ctx *ctx, uint8_t *dst, const uint32_t *h_idx, const uint8_t *h_val, size_t n);
+int launch_scatter16(bk_ctx *ctx, uint16_t *dst, const uint32_t *h_idx, const uint16_t *h_val, size_t n);
 // the owned rows of the lensmap as the reference leaves them when its scan stops at the pixel with scan key bad_key - 1 (everything it
 // had not reached yet NULL) and the display flags of what is left; synchronous
 int launch_truncate_scan(bk_ctx *ctx, unsigned int bad_key, int display_out[BK_MAX_PLATES]);
@@ -243,6 +252,9 @@ int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst_first_o
 // (a NULL plate: one that no lensmap entry of the owned rows names); dst = the first owned row at the origin; ss2: of the half-size frame
 int launch_apply_rgba_fb(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
                          const uint8_t *d_lut, bool ss2);
+// the same frame with every pixel blended from the four texels around its sub-texel position (ctx->d_subtexel, which must be there)
+int launch_apply_rgba_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
+                                  const uint8_t *d_lut);
 int coopmap_stats(bk_ctx *ctx, int out[6]);   // blocks, direct-gather blocks, empty blocks, LDS bytes per buffer
 int coopmap_traffic_model(bk_ctx *ctx, uint64_t out[8]);
 int coopmap_xcd_probe(bk_ctx *ctx, int *out, int nwg);

@@ -170,7 +170,7 @@ static HostModuleP load_host_module(const std::string &so)
     m->corners = (decltype(m->corners))dlsym(dl, "bk_hostmod_corners");
     m->texel_owns = (decltype(m->texel_owns))dlsym(dl, "bk_hostmod_texel_owns");
     m->inverse_scan = (decltype(m->inverse_scan))dlsym(dl, "bk_hostmod_inverse_scan");
-    if (!abi || abi() != 4 + (int)sizeof(BkBuildParams) * 16 || !m->inverse || !m->corners || !m->texel_owns || !m->inverse_scan) return nullptr;
+    if (!abi || abi() != 5 + (int)sizeof(BkBuildParams) * 16 || !m->inverse || !m->corners || !m->texel_owns || !m->inverse_scan) return nullptr;
     return m;
 }
 

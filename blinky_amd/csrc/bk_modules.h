@@ -23,10 +23,10 @@ struct CodeResult {
 struct HostModule {
     void *dl = nullptr;
     int fd = -1;                       // the descriptor the object was verified and loaded through; kept open: see load_host_module
-    void (*inverse)(const BkBuildParams *, const unsigned int *, int, unsigned long, unsigned int *, unsigned char *, int *, int *) = nullptr;
+    void (*inverse)(const BkBuildParams *, const unsigned int *, int, unsigned long, unsigned int *, unsigned char *, unsigned short *, int *, int *) = nullptr;
     void (*corners)(const BkBuildParams *, const unsigned int *, int, unsigned long, int *, int *, unsigned char *, int *) = nullptr;
     void (*texel_owns)(const BkBuildParams *, const unsigned int *, int, unsigned long, unsigned char *) = nullptr;
-    int (*inverse_scan)(const BkBuildParams *, unsigned int *, unsigned char *, int *) = nullptr;
+    int (*inverse_scan)(const BkBuildParams *, unsigned int *, unsigned char *, unsigned short *, int *) = nullptr;
     ~HostModule() { if (dl) dlclose(dl); if (fd >= 0) close(fd); }
 };
 using HostModuleP = std::shared_ptr<HostModule>;

@@ -71,6 +71,9 @@ _SIGS = {
     "bk_set_async_compile": (_i, [_vp, _i]),
     "bk_set_lensmap": (_i, [_vp, _vp, _vp]),
     "bk_read_lensmap": (_i, [_vp, _vp, _vp]),
+    "bk_set_subtexel": (_i, [_vp, _i]),
+    "bk_read_subtexel": (_i, [_vp, _vp]),
+    "bk_set_lensmap_subtexel": (_i, [_vp, _vp]),
     "bk_upload_plate": (_i, [_vp, _i, _i, _vp, _i]),
     "bk_upload_plate_async": (_i, [_vp, _i, _i, _vp, _i]),
     "bk_upload_plate_rgba": (_i, [_vp, _i, _i, _vp, _i]),
@@ -82,6 +85,7 @@ _SIGS = {
     "bk_apply_rgba_tinted_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
     "bk_apply_rgba_ss2_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
     "bk_apply_rgba_fb_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp, _i]),
+    "bk_apply_rgba_fb_bilinear_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp]),
     "bk_debug_fb_decode_check": (C.c_longlong, [_i, _i]),
     "bk_globe_device_ptr": (_vp, [_vp, _i]),
     "bk_fill_plate_lcg": (_i, [_vp, _i, _i, C.c_uint32]),
@@ -123,6 +127,7 @@ _SIGS = {
     "bk_debug_stream_mix": (_i, [_vp, _sz, _i, _i, C.POINTER(_d)]),
     "bk_debug_fnv1a64": (_i, [_vp, _sz, C.POINTER(C.c_uint64)]),
     "bk_debug_host_build": (_i, [_vp, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_d)]),
+    "bk_debug_host_build_subtexel": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_d)]),
     "bk_debug_resident_latency": (_i, [_vp, _i, _vp, _i, _i, C.POINTER(_d), C.POINTER(_d)]),
     "bk_debug_build_params": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "bk_debug_host_entries": (_i, [_vp, _vp, _sz, _vp, _vp]),
@@ -339,6 +344,23 @@ class Context:
                 raise BlinkyError(f"[{rc}] {err}")
         return off, tin, list(disp), scale.value, err
 
+    def host_build_subtexel(self, mode=0):
+        """host_build with the sub-texel plane (bk_debug_host_build_subtexel): (offsets, tints, sub uint16 [rows * W], display, scale, error
+        text or None)"""
+        W, H, ps, r0, r1 = self.size()
+        off = np.empty((r1 - r0) * W, np.uint32)
+        tin = np.empty((r1 - r0) * W, np.uint8)
+        sub = np.empty((r1 - r0) * W, np.uint16)
+        disp = (_i * MAX_PLATES)()
+        scale = _d()
+        rc = lib.bk_debug_host_build_subtexel(self._h, int(mode), _ptr(off), _ptr(tin), _ptr(sub), disp, C.byref(scale))
+        err = None
+        if rc != OK:
+            err = lib.bk_last_error(self._h).decode(errors="replace")
+            if rc != -3:                                     # (BK_E_SCRIPT: the table is in place)
+                raise BlinkyError(f"[{rc}] {err}")
+        return off, tin, sub, list(disp), scale.value, err
+
     def last_build_path(self):
         """(path, why) of the last build(): 0 GPU kernels, 1 host worker pool, 2 one sequential host scan"""
         buf = C.create_string_buffer(1024)
@@ -381,6 +403,24 @@ class Context:
         tin = np.empty((r1 - r0) * w, np.uint8)
         self._chk(lib.bk_read_lensmap(self._h, _ptr(off), _ptr(tin)))
         return off, tin
+
+    def set_subtexel(self, on):
+        """keep (or stop keeping) the sub-texel plane beside the lensmap: uint16 [rows * W], qx | qy << 8, 0x8080 = a texel's centre"""
+        self._chk(lib.bk_set_subtexel(self._h, int(on)))
+
+    def read_subtexel(self):
+        w, h, ps, r0, r1 = self.size()
+        sub = np.empty((r1 - r0) * w, np.uint16)
+        self._chk(lib.bk_read_subtexel(self._h, _ptr(sub)))
+        return sub
+
+    def set_lensmap_subtexel(self, sub):
+        """after set_lensmap (which resets the plane to centres): the plane of the table just set"""
+        w, h, ps, r0, r1 = self.size()
+        sub = np.ascontiguousarray(sub, dtype=np.uint16).reshape(-1)
+        if sub.size != (r1 - r0) * w:
+            raise ValueError(f"sub must have {(r1 - r0) * w} entries, not {sub.size}")
+        self._chk(lib.bk_set_lensmap_subtexel(self._h, _ptr(sub)))
 
     # globe
     def upload_plate(self, frame, plate, src, pitch=None):
@@ -504,6 +544,20 @@ class Context:
             if lut.shape != (4, MAX_PLATES, 256):
                 raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
         self._chk(lib.bk_apply_rgba_fb_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut), int(ss2)))
+
+    def apply_rgba_fb_bilinear_device(self, plates, pitches, dst_ptr, dst_pitch, x0=0, y0=0, lut=None):
+        """apply_rgba_fb_device with bilinear texel filtering through the sub-texel plane (set_subtexel(True) before the build): every
+        mapped pixel is the exact integer blend of the four texels of its own plate around its position; a tint is applied to each
+        texel before the blend.  Reads texels within one texel of a named one, clamped to the plate"""
+        if len(plates) != MAX_PLATES or len(pitches) != MAX_PLATES:
+            raise ValueError(f"plates and pitches must have {MAX_PLATES} entries")
+        pp = (_vp * MAX_PLATES)(*[p.value if isinstance(p, C.c_void_p) else p for p in plates])
+        pi = (_i * MAX_PLATES)(*[int(p) for p in pitches])
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8)
+            if lut.shape != (4, MAX_PLATES, 256):
+                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        self._chk(lib.bk_apply_rgba_fb_bilinear_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut)))
 
     # ---- the resident single-frame apply (bk_apply_resident_*): one kernel stays on the device, frames are commands
     def resident_begin(self, rubix_on=False, pal=None, idle_ms=0.0):

@@ -186,6 +186,25 @@ int bk_last_build_fixups(const bk_ctx *ctx, int *flagged, int *changed);
 /* direct access to the table (lens.pixels / lens.pixel_tints of the owned rows) */
 int bk_set_lensmap(bk_ctx *ctx, const uint32_t *offsets, const uint8_t *tints);
 int bk_read_lensmap(bk_ctx *ctx, uint32_t *offsets, uint8_t *tints);
+/* The SUB-TEXEL plane (no counterpart in the reference, which keeps (int)(u * platesize), fisheye.c:1988, of the plate position it
+ * computes at :2055-2062, and so can only ever show one nearest texel): uint16 [rows][W] beside the lensmap, owned rows only, as the
+ * tints are.  For a mapped entry of an inverse map, with U = u * platesize and px = (int)U: qx = (int)((U - px) * 256), 0..255, qy
+ * likewise, sub = qx | qy << 8 - exact and reproducible: from the narrowed float ray on, host and device perform the same IEEE
+ * operations, U - px is exact and so is * 256; entries the host re-derives (bk_last_build_fixups) have their sub re-derived too
+ * (`changed` keeps counting offsets and tints only).  0x8080, the texel's centre, is the value of every entry that has no position of
+ * its own: NULL entries, every entry of a FORWARD map (the quad rasteriser has no per-pixel uv), every entry after bk_set_lensmap,
+ * entries NULLed by bk_truncate_build, the empty map a failed build leaves.
+ * bk_set_subtexel(ctx, 1) opts in (default 0: no plane is allocated, the build kernel stores nothing, every existing path, count and
+ * timing is as it was).  On: every later bk_build fills the plane, whichever path it takes (GPU kernels, host worker pool,
+ * sequential scan), and bk_set_lensmap resets it to centres.  The plane lives and dies with the lensmap: gone after bk_resize /
+ * bk_set_rows, left as it was by a bk_build that returns BK_PENDING.  Switching on over a lensmap already in place conjures no
+ * plane: it is absent until the next bk_build, bk_set_lensmap or bk_set_lensmap_subtexel.  Switching off frees it.
+ * bk_read_subtexel copies the plane out; bk_set_lensmap_subtexel replaces it (call it after bk_set_lensmap).  BK_E_STATE from either
+ * without a lensmap or with the switch off, and from bk_read_subtexel while the plane is absent.
+ * Memory: 2 bytes per pixel of the owned rows (16.6 MB at 3840x2160).  Reader: bk_apply_rgba_fb_bilinear_device. */
+int bk_set_subtexel(bk_ctx *ctx, int on);
+int bk_read_subtexel(bk_ctx *ctx, uint16_t *out);
+int bk_set_lensmap_subtexel(bk_ctx *ctx, const uint16_t *sub);
 
 /* ---- globe plates -------------------------------------------------------------------
  * bk_upload_plate replaces render_plate's row memcpy loop (fisheye.c:2441-2449):
@@ -360,10 +379,33 @@ int bk_apply_rgba_ss2_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev
  * 45.3 / 72.0 and 63.2 / 128.2; ss2 45.1 / 61.0 and 67.8 / 110.6 - and it saves the 112.8 MB of ring a 4K globe takes.  The staged
  * apply ALONE is faster (27.6 and 40.6 us plain): a host whose globes stay resident for many frames stays with bk_apply_rgba_device.
  * Out of scope: more than one frame per call; a host-pointer form; the resident kernel; the bk_comm_* / bk_multi_* exchanges (stripe
- * CONTEXTS - bk_set_rows - do work); the drop-in fisheye_hip.c, whose engine is 8-bit; texel filtering (one nearest texel per sample). */
+ * CONTEXTS - bk_set_rows - do work); the drop-in fisheye_hip.c, whose engine is 8-bit; texel filtering (one nearest texel per sample: bk_apply_rgba_fb_bilinear_device below filters). */
 int bk_apply_rgba_fb_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
                             void *dst_dev, int dst_pitch, int x0, int y0,
                             const uint8_t lut[4][BK_MAX_PLATES][256] /* nullable: NULL = plain, else tinted */, int ss2);
+/* bk_apply_rgba_fb_bilinear_device: bk_apply_rgba_fb_device (ss2 = 0) with BILINEAR texel filtering - the answer to magnification (a
+ * fisheye at f_fov 180 stretches the centre plate's texels over several pixels), as ss2 is the answer to minification.  The reference
+ * keeps (int)(u * platesize) (fisheye.c:1988) of the position it computes (:2055-2062); the sub-texel plane (bk_set_subtexel above)
+ * keeps the next eight bits, and this call blends the four texels around the position.
+ * Sources, destination, origin, owned rows, untouched unmapped pixels, alignment classes, NULL plates and errors are those of
+ * bk_apply_rgba_fb_device; in addition BK_E_STATE when the context has no sub-texel plane.
+ * Semantics per mapped pixel (integer, exact), with (px, py) the entry's texel and sub = qx | qy << 8 - texel centres sit at px + 1/2:
+ *     sx = qx + 128;  xa = px - 1 + (sx >> 8);  fx = sx & 255;  xb = xa + 1;  xa, xb clamped to [0, ps - 1]      (ya, yb, fy alike)
+ *     per byte c of the texels a00 a01 (row ya), a10 a11 (row yb), all of the entry's OWN plate:
+ *         h0 = a00 * (256 - fx) + a01 * fx;  h1 = a10 * (256 - fx) + a11 * fx;  out = (h0 * (256 - fy) + h1 * fy + 32768) >> 16
+ * Clamp-to-edge is per plate: filtering ACROSS A CUBE SEAM is out of scope (the last texel row of a plate is repeated, not blended
+ * with the neighbouring plate's).  lut given: each of the four texels goes through the pixel's tint (lut[c][t][v], tints >=
+ * BK_MAX_PLATES leave it as it is) BEFORE the blend, as ss2 tints per sample before its average.  A constant plate gives that
+ * constant; a plane that is 0x8080 everywhere gives bk_apply_rgba_fb_device's frame byte for byte.
+ * THE CONTRACT ON READS, restated: texels within ONE TEXEL of a texel some lensmap entry of the owned rows names, clamped to the
+ * plate, may be read - also where their weight is 0.  A renderer that scissors to bk_plate_footprint's rect must grow it by one texel
+ * on every side, clipped to the plate.
+ * Measured: tools/bench_rgba.py --fb --bilinear [--tint], profiles/rgba_fb_bilinear_apply.txt.
+ * Out of scope: the staged ring applies (their block map lists exactly the 16-byte chunks a block reads), ss2 combined with the
+ * blend, the resident kernel, the bk_comm_* / bk_multi_* exchanges, the drop-in fisheye_hip.c, whose engine is 8-bit. */
+int bk_apply_rgba_fb_bilinear_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
+                                     void *dst_dev, int dst_pitch, int x0, int y0,
+                                     const uint8_t lut[4][BK_MAX_PLATES][256] /* nullable: NULL = plain, else tinted */);
 
 /* ---- resident single-frame apply ------------------------------------------------------------------------------------
  * replaces: the per-frame call of render_lensmap (fisheye.c:803 -> 2406-2424) for hosts whose globes stay in device memory.

@@ -63,6 +63,10 @@ int         bk_debug_stream_mix(bk_ctx *ctx, size_t bytes, int period, int write
  * device-less one included: mode 1 = worker pool, 2 = one sequential scan in the reference's order, 0 = what bk_build would choose.
  * offsets [rows * W] come back in the reference's layout (plate * ps * ps + py * ps + px, 0xFFFFFFFF = NULL); returns what bk_build returns */
 int         bk_debug_host_build(bk_ctx *ctx, int mode, uint32_t *offsets, uint8_t *tints, int display_out[BK_MAX_PLATES], double *scale_out);
+/* the same with the sub-texel plane the build keeps under bk_set_subtexel (blinky_hip.h; what fisheye.c:1988 drops of :2055-2062):
+ * sub [rows * W], qx | qy << 8, 0x8080 for NULL entries and every entry of a forward map.  The context's switch plays no part. */
+int         bk_debug_host_build_subtexel(bk_ctx *ctx, int mode, uint32_t *offsets, uint8_t *tints, uint16_t *sub, int display_out[BK_MAX_PLATES],
+                                         double *scale_out);
 /* FNV-1a-64 of a HOST buffer - the hash tests/golden/lensmaps.json pins frames with (bench.py --check) */
 int         bk_debug_fnv1a64(const void *host, size_t bytes, uint64_t *out);
 /* the resident apply one frame at a time, on the C host's clock (what fisheye_hip.c pays, without a binding in between): `frames`

@@ -7,7 +7,7 @@ At 3840x2160 cube/panini and cube/hammer, over the 64-slot LCG ring of the bench
 B's output is compared with A's plane by plane before anything is timed.  Timing: HIP events on the context's stream, warm-up
 launches first, regions of at least --region seconds made of ten event-timed trains of launches (a region's figure is the median
 train), A / B / A / B ... alternated --repeats times inside this one process.  The target: B's median <= A's median + A's own spread
-(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2] [--upload] [--fb]
+(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2] [--upload] [--fb [--bilinear]]
 
 --tint: the same protocol for f_rubix on truecolour frames, three launches alternated A' / B' / B:
   A'  one bk_apply_device launch of 64 8-bit frames with rubix_on = 1 (existing code: the same bytes through the same number of LUT
@@ -40,7 +40,15 @@ D's frame must equal B + P's byte for byte before anything is timed.  The source
 16-byte aligned) advanced every frame, so the texels come from HBM and not from the Infinity Cache; B + P also rotates through 16
 truecolour globes.  --repeats blocks of --reps frames each way; a figure is the median of the block medians, its spread their max - min.
 The expectation: D < B + P by more than the two spreads together; D against P alone is printed beside it (what a caller whose globes
-stay resident would pay)."""
+stay resident would pay).
+
+--fb --bilinear [--tint] [--reps 31]: bilinear texel filtering against the nearest-texel launch it extends, alternated frame by frame:
+  D  bk_apply_rgba_fb_device (--tint: with the tables) - existing code
+  L  bk_apply_rgba_fb_bilinear_device from the same plates through the sub-texel plane the build kept (bk_set_subtexel)
+L's frame must equal the numpy model of tests/subtexel_model.py at full size before anything is timed.  The same ring of 16 plate sets
+and the same fill in front of every timed frame as --fb.  There is no pass / fail ratio: L reads the 16.6 MB plane on top of D's bytes and
+up to three neighbours per pixel that mostly share the named texel's lines; L, D, L / D and the spreads are printed.  The build's side is
+timed too: bk_build of the same lens with the switch off and on, alternated (--repeats pairs, bk_last_build_ms)."""
 import argparse
 import json
 import os
@@ -435,6 +443,116 @@ def measure_fb(lens, repeats, reps, tint, ss2):
                 d_model_gb_s=model_d / med["d"] / 1e3, target_met=bool(med["d"] + spread["d"] + spread["bp"] < med["bp"]))
 
 
+def measure_fb_bilinear(lens, repeats, reps, tint):
+    """D (bk_apply_rgba_fb_device) against L (bk_apply_rgba_fb_bilinear_device), frame by frame, from the ring of measure_fb"""
+    import subtexel_model as SM
+    SETS = SLOTS // 4
+    ctx = blinky_amd.Context(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_frames(1)
+    S.configure(ctx, "cube", lens, None, (W, H))
+    # the build with the switch off and on, alternated: what the extra 2 bytes per pixel cost it
+    build_ms = {"off": [], "on": []}
+    ctx.build()
+    for _ in range(repeats):
+        for name, on in (("off", False), ("on", True)):
+            ctx.set_subtexel(on)
+            ctx.build()
+            build_ms[name].append(ctx.last_build_ms())
+    display, _ = ctx.build()                                # (the switch is on)
+    fixups = ctx.last_build_fixups()
+    ps = min(W, H)
+    shown = [p for p in range(6) if p < len(display) and display[p]]
+    lut = None
+    if tint:
+        pal = blinky_amd.ffi.create_palmap(((np.arange(768) * 37) % 256).astype(np.uint8))
+        lut = np.ascontiguousarray(np.broadcast_to(pal, (4, 6, 256)))
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    src = [[torch.randint(0, 256, (ps, ps, 4), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(6)] for _ in range(SETS)]
+    pitch = 4 * ps
+    assert all(t.data_ptr() % 16 == 0 for s in src for t in s) and pitch % 16 == 0
+    ptrs = [[src[s][p].data_ptr() if p in shown else None for p in range(6)] for s in range(SETS)]
+    pitches = [pitch] * 6
+    out = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")
+    plug = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+
+    def nearest(s):
+        ctx.apply_rgba_fb_device(ptrs[s], pitches, out.data_ptr(), 4 * W, lut=lut)
+
+    def bilinear(s):
+        ctx.apply_rgba_fb_bilinear_device(ptrs[s], pitches, out.data_ptr(), 4 * W, lut=lut)
+
+    # before anything is timed: L's frame is the numpy model's, at full size, in the flavour that is timed (in bands of rows: the model
+    # keeps several int64 arrays of a band's size)
+    off, tints = ctx.read_lensmap()
+    sub = ctx.read_subtexel()
+    plates = np.stack([src[0][p].cpu().numpy() for p in range(6)])
+    bilinear(0)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy().reshape(H, 4 * W)
+    want = np.zeros((H, 4 * W), np.uint8)
+    for r0 in range(0, H, 120):
+        SM.bilinear_frame(plates, off, sub, tints, W, H, ps, (r0, min(H, r0 + 120)), lut, want, 0, 0)
+    if not np.array_equal(got, want):
+        raise SystemExit(f"{lens}: the bilinear frame differs from the numpy model in {int((got != want).sum())} bytes - nothing timed")
+    mapped = int((off != 0xFFFFFFFF).sum())
+    moved = int((sub[off != 0xFFFFFFFF] != SM.CENTRE).sum())
+    del off, tints, sub, plates, got, want
+    for k in range(2 * SETS):                              # warm-up: every set once each way
+        (bilinear if k % 2 else nearest)(k % SETS)
+    torch.cuda.synchronize()
+    blocks = {"d": [], "l": []}
+    k = 0
+    for _ in range(repeats):
+        ev = []
+        for r in range(2 * reps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            plug.fill_(r & 255)
+            e[0].record(stream)
+            (bilinear if r % 2 else nearest)(k % SETS)
+            e[1].record(stream)
+            ev.append(e)
+            k += 1
+        torch.cuda.synchronize()
+        blocks["d"].append(statistics.median(e[0].elapsed_time(e[1]) * 1e3 for e in ev[0::2]))
+        blocks["l"].append(statistics.median(e[0].elapsed_time(e[1]) * 1e3 for e in ev[1::2]))
+    fp = [ctx.plate_footprint(p) for p in range(6)]
+    ctx.close()
+    med = {n: statistics.median(v) for n, v in blocks.items()}
+    spread = {n: max(v) - min(v) for n, v in blocks.items()}
+    tiles = sum(fp[p][1] for p in shown)
+    model_d = 4 * W * H + (1 if tint else 0) * W * H + 4 * mapped + 4 * 128 * tiles      # measure_fb's estimate of D's bytes
+    return dict(lens=lens, W=W, H=H, ps=ps, tint=bool(tint), bilinear=True, displayed_plates=shown, frames_per_block=reps, blocks=repeats,
+                footprint_tiles=[fp[p][1] for p in range(6)], mapped_pixels=mapped, pixels_off_centre=moved, fixups=list(fixups),
+                model_bytes_d=model_d, model_bytes_l=model_d + 2 * W * H, blocks_us=blocks, median_us=med, spread_us=spread,
+                l_over_d=med["l"] / med["d"], bytes_l_over_d=(model_d + 2 * W * H) / model_d, build_ms=build_ms,
+                build_median_ms={n: statistics.median(v) for n, v in build_ms.items()},
+                build_spread_ms={n: max(v) - min(v) for n, v in build_ms.items()})
+
+
+def main_fb_bilinear(args):
+    rows = []
+    what = "tinted" if args.tint else "plain"
+    for lens in args.lenses.split(","):
+        r = measure_fb_bilinear(lens, args.repeats, max(31, args.reps), args.tint)
+        rows.append(r)
+        m, s, b = r["median_us"], r["spread_us"], r["blocks_us"]
+        bm, bs = r["build_median_ms"], r["build_spread_ms"]
+        print(f"4K cube/{lens}, one {what} truecolour frame per call from device plates (16-byte aligned, a ring of 16 sets), plates {r['displayed_plates']} "
+              f"displayed, {r['mapped_pixels']} mapped pixels of which {r['pixels_off_centre']} off their texel's centre, {r['blocks']} blocks of "
+              f"{r['frames_per_block']} frames each way, D / L alternated:\n"
+              f"  D  bk_apply_rgba_fb_device           {m['d']:8.1f} us (blocks {fmt(b['d'])}; spread {s['d']:.1f})  estimate {r['model_bytes_d'] / 1e6:.1f} MB\n"
+              f"  L  bk_apply_rgba_fb_bilinear_device  {m['l']:8.1f} us (blocks {fmt(b['l'])}; spread {s['l']:.1f})  estimate {r['model_bytes_l'] / 1e6:.1f} MB\n"
+              f"  L == the numpy model at full size; L / D = {r['l_over_d']:.3f} (bytes alone: {r['bytes_l_over_d']:.3f})\n"
+              f"  bk_build, switch off / on alternated: {bm['off']:.3f} / {bm['on']:.3f} ms (runs {fmt(r['build_ms']['off'])} / {fmt(r['build_ms']['on'])}; "
+              f"spreads {bs['off']:.3f} / {bs['on']:.3f}); fix-ups (flagged, changed) {r['fixups']}", flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main_fb(args):
     rows = []
     what = ("ss2 " if args.ss2 else "") + ("tinted" if args.tint else "plain")
@@ -526,10 +644,15 @@ def main():
     ap.add_argument("--ss2", action="store_true", help="2x2 supersampling: full-size truecolour launch A (with --tint: the tinted one) / fused ss2 launch B")
     ap.add_argument("--upload", action="store_true", help="the per-frame loop: full plate uploads A / footprint uploads B / the one-frame apply P behind them")
     ap.add_argument("--fb", action="store_true", help="one frame per call: footprint uploads + the staged one-frame apply B + P / bk_apply_rgba_fb_device D (with --tint / --ss2: the matching pairs)")
+    ap.add_argument("--bilinear", action="store_true", help="with --fb: bk_apply_rgba_fb_device D / bk_apply_rgba_fb_bilinear_device L (with --tint: both through the tables), and bk_build with the sub-texel plane off / on")
     ap.add_argument("--reps", type=int, default=31, help="--upload / --fb: frames each way per block (at least 31)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_rgba.py measures on the GPU; there is none here")
+    if args.bilinear:
+        if not args.fb or args.ss2:
+            raise SystemExit("--bilinear goes with --fb (and not with --ss2)")
+        return main_fb_bilinear(args)
     if args.fb:
         return main_fb(args)
     if args.upload:
