@@ -159,6 +159,7 @@ extern "C" void bk_destroy(bk_ctx *ctx)
     hipFree(ctx->d_pal);
     hipFree(ctx->d_lut_rgba);
     hipFree(ctx->d_lut_fb);
+    hipFree(ctx->d_seam);
     hipFree(ctx->d_display);
     hipFree(ctx->d_flag_list);
     for (void *q : ctx->fwd_scratch) hipFree(q);
@@ -240,6 +241,7 @@ void bk::empty_context(bk_ctx *ctx)
     ctx->row0 = ctx->row1 = 0;
     ctx->lensmap_valid = false;
     ctx->subtexel_valid = false;
+    bk::seam_drop(ctx);
     ctx->spans_valid = false;
     ctx->err = msg;
 }
@@ -251,6 +253,7 @@ extern "C" int bk_resize(bk_ctx *ctx, int width, int height)
     ctx->clear_debug_corners();                 // (a test's corner table was sized for the platesize that was)
     if (ctx->device < 0) {                      // host-only: geometry for calc_zoom / code generation
         if (width == ctx->W && height == ctx->H) return BK_OK;      // (as with a device: the size it has already changes nothing, a stripe stays)
+        bk::seam_drop(ctx);
         ctx->W = width; ctx->H = height; ctx->ps = std::min(width, height); ctx->gp = (ctx->ps + 63) & ~63;
         ctx->ph = (ctx->ps + 7) & ~7;
         ctx->row0 = 0; ctx->row1 = height;
@@ -274,6 +277,7 @@ extern "C" int bk_resize(bk_ctx *ctx, int width, int height)
     ctx->row0 = 0; ctx->row1 = height;
     ctx->lensmap_valid = false;
     ctx->subtexel_valid = false;
+    bk::seam_drop(ctx);                                     // (made for the platesize that was; a caller-set one goes with it)
     bk::footprint_invalidate(ctx);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail_empty(ctx->fail(BK_E_HIP, "bk_resize: hipStreamSynchronize failed"));
     (void)hipFree(ctx->d_plate_stage);
@@ -965,6 +969,92 @@ extern "C" int bk_apply_rgba_fb_bilinear_device(bk_ctx *ctx, const void *const p
         if (int r = upload_lut_fb(ctx, lut)) return r;
     uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
     return bk::launch_apply_rgba_fb_bilinear(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->d_lut_fb : nullptr);
+}
+
+// ---- the seam table: which texel of which plate lies one step outside every plate's four edges ----------------------------------
+int bk::seam_table_ready(bk_ctx *ctx, const char *who)
+{
+    if (ctx->seam_valid) return BK_OK;
+    if (!ctx->globe_valid || ctx->numplates < 1) return ctx->fail(BK_E_STATE, "%s: no valid globe to make the seam table for (bk_load_globe / bk_set_globe_plates)", who);
+    if (ctx->ps < 1) return ctx->fail(BK_E_STATE, "%s: no size to make the seam table for (bk_resize)", who);
+    if (int r = bk::seam_table_compute(ctx, ctx->seam_table)) return r;
+    ctx->seam_valid = true;
+    ctx->seam_user = false;
+    ctx->d_seam_current = false;
+    return BK_OK;
+}
+
+extern "C" int bk_read_seam_table(bk_ctx *ctx, uint32_t *out)
+{
+    if (!ctx || !out) return BK_E_INVALID;
+    if (int r = bk::seam_table_ready(ctx, "bk_read_seam_table")) return r;
+    memcpy(out, ctx->seam_table.data(), ctx->seam_table.size() * sizeof(uint32_t));
+    return BK_OK;
+}
+
+extern "C" int bk_set_seam_table(bk_ctx *ctx, const uint32_t *table)
+{
+    if (!ctx || !table) return BK_E_INVALID;
+    if (ctx->ps < 1) return ctx->fail(BK_E_STATE, "bk_set_seam_table: no size (bk_resize first)");
+    const size_t n1 = (size_t)ctx->ps + 2, n = (size_t)BK_MAX_PLATES * 4 * n1;
+    const uint64_t texels = (uint64_t)BK_MAX_PLATES * (uint64_t)ctx->ps * (uint64_t)ctx->ps;
+    for (size_t k = 0; k < n; ++k)
+        if (table[k] != BK_NULL_OFFSET && (uint64_t)table[k] >= texels)
+            return ctx->fail(BK_E_INVALID, "bk_set_seam_table: entry %zu (%u) is neither NULL nor a texel of the globe (below %llu)", k, table[k],
+                             (unsigned long long)texels);
+    for (size_t p = 0; p < (size_t)BK_MAX_PLATES; ++p) {
+        const uint32_t *e = table + p * 4 * n1;         // (row y = -1, row y = ps, column x = -1, column x = ps)
+        if (e[0] != e[2 * n1] || e[n1 - 1] != e[3 * n1] || e[n1] != e[3 * n1 - 1] || e[2 * n1 - 1] != e[4 * n1 - 1])
+            return ctx->fail(BK_E_INVALID, "bk_set_seam_table: plate %zu: a corner's two copies differ", p);
+    }
+    ctx->seam_table.assign(table, table + n);
+    ctx->seam_valid = ctx->seam_user = true;
+    ctx->d_seam_current = false;
+    return BK_OK;
+}
+
+// ctx->seam_table decoded into ctx->d_seam, once per table
+static int seam_upload(bk_ctx *ctx)
+{
+    if (ctx->d_seam_current) return BK_OK;
+    const size_t n = ctx->seam_table.size();
+    if (n > ctx->d_seam_words || !ctx->d_seam) {
+        BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipFree(ctx->d_seam);
+        ctx->d_seam = nullptr; ctx->d_seam_words = 0;
+        BK_HIP(ctx, hipMalloc((void **)&ctx->d_seam, n * sizeof(uint2)));
+        ctx->d_seam_words = n;
+    }
+    const uint32_t ps = (uint32_t)ctx->ps, pb = (uint32_t)ctx->gp * (uint32_t)ctx->ph;
+    std::vector<uint2> dec(n);
+    for (size_t k = 0; k < n; ++k) {
+        const uint32_t e = ctx->seam_table[k];
+        if (e == BK_NULL_OFFSET) { dec[k] = make_uint2(BK_NULL_OFFSET, 0u); continue; }
+        const uint32_t q = e / (ps * ps), rem = e - q * ps * ps, py = rem / ps, px = rem - py * ps;
+        dec[k] = make_uint2(q * pb, py << 16 | px);     // (the plate as its first device offset: the kernel picks it by comparisons; ps < 2^15)
+    }
+    // (a pageable source: the copy has left `dec` when the call returns)
+    BK_HIP(ctx, hipMemcpyAsync(ctx->d_seam, dec.data(), n * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->d_seam_current = true;
+    return BK_OK;
+}
+
+// bk_apply_rgba_fb_bilinear_device with each of the four positions resolved on its own: one outside the plate is the seam table's texel
+extern "C" int bk_apply_rgba_fb_bilinear_seams_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
+                                                      void *dst_dev, int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256])
+{
+    static const char *who = "bk_apply_rgba_fb_bilinear_seams_device";
+    if (int r = fb_apply_args(ctx, who, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, 0)) return r;
+    if (!ctx->subtexel_valid || !ctx->d_subtexel)
+        return ctx->fail(BK_E_STATE, "%s: the lensmap has no sub-texel plane (bk_set_subtexel(ctx, 1), then bk_build / bk_set_lensmap)", who);
+    if (int r = bk::seam_table_ready(ctx, who)) return r;
+    if (int r = seam_upload(ctx)) return r;
+    bk::Range range(who);
+    if (lut)
+        if (int r = upload_lut_fb(ctx, lut)) return r;
+    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
+    return bk::launch_apply_rgba_fb_bilinear_seams(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->d_lut_fb : nullptr);
 }
 
 // ---- resident single-frame apply (bk_apply_resident.inc) ------------------------------------------------------------

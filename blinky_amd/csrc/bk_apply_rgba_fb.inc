@@ -278,11 +278,16 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_ss2_kernel(const uint32_t *
 // each; the second per byte as (h0 << 8) + fy * (h1 - h0) - the same number - one signed 24-bit multiply.  Tinted: every one of the
 // four texels goes through bk_fb_tint first, as ss2 tints per sample before its average.
 // As built (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; no scratch): plain / tinted 49 / 66 VGPRs = 8 / 7 waves per SIMD.
-// Measured: tools/bench_rgba.py --fb --bilinear [--tint], profiles/rgba_fb_bilinear_apply.txt.
+// SEAMS (bk_apply_rgba_fb_bilinear_seams_device): the same common path, then one wave-uniform branch into the seam pass (below);
+// as built 68 / 78 VGPRs = 7 / 6 waves per SIMD, no scratch - a wave less than the kernel without it, and the measured price: at 4K
+// S / L = 1.12 / 1.03 / 1.08 plain and 1.14 / 1.14 / 1.14 tinted (panini / hammer / quincuncial), the target S <= L + both spreads
+// MISSED everywhere (profiles/rgba_fb_bilinear_seams_apply.txt).  Suspected, not shown by a counter pass: the occupancy, since under
+// 0.1 % of the pixels take the pass.  What was tried: the pass before the common loads (80 / 84), after them with the decode kept (84 / 90).
+// Measured: tools/bench_rgba.py --fb --bilinear [--seams] [--tint], profiles/rgba_fb_bilinear_apply.txt.
 
-// bk_fb_texel's decode with the parts handed out: the plate's base, its pitch, the texel's column and row
-__device__ __forceinline__ void bk_fb_locate(const BkFbPlates &s, const BkFbGeom &g, uint32_t off, const uint8_t *&base, uint32_t &pitch, uint32_t &px,
-                                             uint32_t &py)
+// bk_fb_texel's decode with the parts handed out: the plate's base, its pitch, the texel's column and row (and the plate's number)
+__device__ __forceinline__ uint32_t bk_fb_locate(const BkFbPlates &s, const BkFbGeom &g, uint32_t off, const uint8_t *&base, uint32_t &pitch, uint32_t &px,
+                                                 uint32_t &py)
 {
     // (selects on the five comparisons, as in bk_fb_texel: picked by the plate's number the struct is copied to scratch)
     const bool c1 = off >= g.pb, c2 = off >= 2u * g.pb, c3 = off >= 3u * g.pb, c4 = off >= 4u * g.pb, c5 = off >= 5u * g.pb;
@@ -290,6 +295,35 @@ __device__ __forceinline__ void bk_fb_locate(const BkFbPlates &s, const BkFbGeom
     base = c5 ? s.p[5] : c4 ? s.p[4] : c3 ? s.p[3] : c2 ? s.p[2] : c1 ? s.p[1] : s.p[0];
     pitch = c5 ? s.pitch[5] : c4 ? s.pitch[4] : c3 ? s.pitch[3] : c2 ? s.pitch[2] : c1 ? s.pitch[1] : s.pitch[0];
     BK_FB_TEXEL(off - plate * g.pb, g.tpr, g.tpr_m, __umulhi, px, py);
+    return plate;
+}
+
+// SEAMS: the four positions of pixel k (a[0..3]: row ya | yb, column xa | xb, already formed clamped to the pixel's own plate) that lie
+// OUTSIDE that plate, through the seam table: seam = uint2 [6][4][n1] {plate * pb or 0xFFFFFFFF, py << 16 | px}, n1 = ps + 2, edge 0 = row -1,
+// 1 = row ps, 2 = column -1, 3 = column ps, index = the coordinate along the edge + 1; a position outside in both axes is the row
+// edge's corner entry.  A NULL entry, or one into a plate passed as NULL, leaves the clamped address.  xr = px + (sx >> 8), yr alike: the
+// pair of columns is xr - 1, xr.  Every lane of the wave issues the four table loads (a lane with nothing outside reads entry 0 and
+// drops it): no load hangs on a divergent branch.  The target's plate arrives as plate * pb and is picked by bk_fb_texel's five comparisons
+// against multiples of pb: selects on the plate's NUMBER become an indexed copy of the struct in scratch.
+__device__ __forceinline__ void bk_fb_seam_resolve(const BkFbPlates &s, const BkFbGeom &g, const uint2 *__restrict__ seam, uint32_t n1, bool mapped, uint32_t plate,
+                                                   uint32_t xr, uint32_t yr, uint32_t ps_m1, const uint32_t *a[4])
+{
+    // (one position at a time, each behind a compiler barrier: the path is rare, and nothing is gained by four entries in flight)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t jx = (uint32_t)j & 1u, jy = (uint32_t)j >> 1;
+        const bool ox = jx ? xr > ps_m1 : xr == 0u, oy = jy ? yr > ps_m1 : yr == 0u;
+        const bool out = mapped && (ox || oy);
+        const uint32_t edge = oy ? jy : 2u + jx, along = oy ? xr + jx : yr + jy;
+        const uint2 e = seam[out ? (plate * 4u + edge) * n1 + (along < n1 ? along : n1 - 1u) : 0u];
+        const uint32_t off = e.x;
+        const bool c1 = off >= g.pb, c2 = off >= 2u * g.pb, c3 = off >= 3u * g.pb, c4 = off >= 4u * g.pb, c5 = off >= 5u * g.pb;
+        const uint8_t *base = c5 ? s.p[5] : c4 ? s.p[4] : c3 ? s.p[3] : c2 ? s.p[2] : c1 ? s.p[1] : s.p[0];
+        const uint32_t pitch = c5 ? s.pitch[5] : c4 ? s.pitch[4] : c3 ? s.pitch[3] : c2 ? s.pitch[2] : c1 ? s.pitch[1] : s.pitch[0];
+        const uint32_t *t = reinterpret_cast<const uint32_t *>(base + (size_t)(e.y >> 16) * pitch + (size_t)(e.y & 0xFFFFu) * 4u);
+        a[j] = out && off != BK_NULL_OFFSET && base ? t : a[j];
+        asm volatile("" ::: "memory");
+    }
 }
 
 // the blend of one pixel: a00 a01 (upper row), a10 a11 (lower row), weights fx, fy in 0..255 of 256
@@ -307,11 +341,13 @@ __device__ __forceinline__ uint32_t bk_fb_blend(uint32_t a00, uint32_t a01, uint
     return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
 }
 
-// sub = the sub-texel plane, [rows][W] as lmap; ps_m1 = platesize - 1; otherwise apply_rgba_fb_kernel's arguments and grid
-template <bool RUBIX>
+// sub = the sub-texel plane, [rows][W] as lmap; ps_m1 = platesize - 1; otherwise apply_rgba_fb_kernel's arguments and grid;
+// SEAMS: seam = the decoded seam table (bk_fb_seam_resolve; unused and NULL otherwise)
+template <bool RUBIX, bool SEAMS>
 __global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint32_t *__restrict__ lmap, const uint8_t *__restrict__ tints,
                                                                      const uint16_t *__restrict__ sub, const BkFbPlates src, const BkFbGeom g, uint32_t ps_m1,
-                                                                     uint8_t *__restrict__ dst, int dst_pitch, const uint8_t *__restrict__ lut)
+                                                                     uint8_t *__restrict__ dst, int dst_pitch, const uint8_t *__restrict__ lut,
+                                                                     const uint2 *__restrict__ seam)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lut_s[RUBIX ? 4 * BK_PAL_BYTES : 16];
     if (RUBIX) bk_fb_load_lut(lut, lut_s);
@@ -331,12 +367,13 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint3
     const uint32_t *spare = lmap + at;               // what an unmapped pixel loads instead of its texels
     const uint32_t *a[16];
     uint32_t fx[4], fy[4];
+    bool rim = false;                                // SEAMS: one of the lane's sixteen positions lies outside its pixel's plate
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const bool mapped = o[k] != BK_NULL_OFFSET;
         const uint8_t *base;
         uint32_t pitch, px, py;
-        bk_fb_locate(src, g, o[k], base, pitch, px, py);
+        (void)bk_fb_locate(src, g, o[k], base, pitch, px, py);
         const uint32_t sx = (q[k] & 255u) + 128u, sy = (q[k] >> 8) + 128u;
         fx[k] = sx & 255u; fy[k] = sy & 255u;
         // the pair px - 1 + (sx >> 8), + 1, clamped to the plate: the left one can only fall below 0, the right one only pass ps - 1
@@ -348,6 +385,7 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint3
         a[4 * k + 1] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xb * 4u) : spare;
         a[4 * k + 2] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xa * 4u) : spare;
         a[4 * k + 3] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xb * 4u) : spare;
+        if (SEAMS) rim |= mapped && (xr == 0u || yr == 0u || xr > ps_m1 || yr > ps_m1);
     }
     uint32_t w[16];
 #pragma unroll
@@ -360,6 +398,46 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint3
             for (int j = 0; j < 4; ++j) w[4 * k + j] = bk_fb_tint(w[4 * k + j], t[k], lut_s);
         }
         v[k] = bk_fb_blend(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3], fx[k], fy[k]);
+    }
+    // SEAMS.  Everything up to here is the kernel without it: every pixel blended from its own plate, clamped.  The seam table's dependent
+    // loads (entry -> plate base and pitch -> address) are taken only by a wave that has a lane on a rim - one uniform branch, under 1 %
+    // of the waves of a 4K frame - and AFTER the common path, when its sixteen addresses and texels are dead: such a wave makes its pixels
+    // again, one at a time, from the entry and the sub (decode, the four clamped addresses, those outside the plate replaced through the
+    // table, four loads, tint, blend).  That was meant to keep the pass's registers below the common path's; as built it does not: the
+    // kernel takes 68 / 78 VGPRs where the one without SEAMS takes 49 / 66, a wave per SIMD less (the head comment has what it costs).
+    // A pixel with nothing outside its plate comes out as it was.
+    if (SEAMS && __any(rim)) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // (the entry and the sub as values the compiler has not seen: otherwise it keeps the common path's decode of all four pixels
+            //  alive down to here instead of taking it again: 84 / 90 VGPRs)
+            uint32_t ok = o[k], qk = q[k];
+            asm volatile("" : "+v"(ok), "+v"(qk));
+            const bool mapped = ok != BK_NULL_OFFSET;
+            const uint8_t *base;
+            uint32_t pitch, px, py;
+            const uint32_t plate = bk_fb_locate(src, g, ok, base, pitch, px, py);
+            const uint32_t sx = (qk & 255u) + 128u, sy = (qk >> 8) + 128u;
+            const uint32_t xr = px + (sx >> 8), yr = py + (sy >> 8);
+            const uint32_t xa = xr ? xr - 1u : 0u, ya = yr ? yr - 1u : 0u;
+            const uint32_t xb = xr < ps_m1 ? xr : ps_m1, yb = yr < ps_m1 ? yr : ps_m1;
+            const uint8_t *ra = base + (size_t)ya * pitch, *rb = base + (size_t)yb * pitch;
+            const uint32_t *b[4];
+            b[0] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xa * 4u) : spare;
+            b[1] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xb * 4u) : spare;
+            b[2] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xa * 4u) : spare;
+            b[3] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xb * 4u) : spare;
+            bk_fb_seam_resolve(src, g, seam, ps_m1 + 3u, mapped, plate, xr, yr, ps_m1, b);
+            uint32_t c[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) c[j] = *b[j];
+            if (RUBIX) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) c[j] = bk_fb_tint(c[j], t[k], lut_s);
+            }
+            v[k] = bk_fb_blend(c[0], c[1], c[2], c[3], sx & 255u, sy & 255u);
+            asm volatile("" ::: "memory");           // (one pixel at a time: four pixels' table entries and texels in flight are registers)
+        }
     }
     uint8_t *out = dst + (size_t)row * dst_pitch + (size_t)x * 4;
     const bool all = o[0] != BK_NULL_OFFSET && o[1] != BK_NULL_OFFSET && o[2] != BK_NULL_OFFSET && o[3] != BK_NULL_OFFSET;      // (entries past W are NULL)
@@ -407,8 +485,8 @@ int launch_apply_rgba_fb(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], c
 }
 
 // dst = pixel (x0, y0 + row0) of the frame; the caller has made sure of the sub-texel plane
-int launch_apply_rgba_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
-                                  const uint8_t *d_lut)
+static int launch_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
+                              const uint8_t *d_lut, bool seams)
 {
     const int rows = ctx->rows();
     if (rows <= 0 || ctx->W <= 0) return BK_OK;
@@ -426,8 +504,29 @@ int launch_apply_rgba_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_P
     g.lmap4 = (ctx->W & 3) == 0;
     const uint32_t ps_m1 = (uint32_t)ctx->ps - 1u;
     const dim3 grid((unsigned)((ctx->W + 127) / 128), (unsigned)((rows + 7) / 8));
-    if (d_lut) hipLaunchKernelGGL(apply_rgba_fb_bilinear_kernel<true>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut);
-    else hipLaunchKernelGGL(apply_rgba_fb_bilinear_kernel<false>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut);
+    const uint2 *seam = seams ? ctx->d_seam : nullptr;
+    if (seams) {
+        if (d_lut) hipLaunchKernelGGL((apply_rgba_fb_bilinear_kernel<true, true>), grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut, seam);
+        else hipLaunchKernelGGL((apply_rgba_fb_bilinear_kernel<false, true>), grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut, seam);
+    } else {
+        if (d_lut) hipLaunchKernelGGL((apply_rgba_fb_bilinear_kernel<true, false>), grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut, seam);
+        else hipLaunchKernelGGL((apply_rgba_fb_bilinear_kernel<false, false>), grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut, seam);
+    }
     BK_HIP(ctx, hipGetLastError());
     return BK_OK;
+}
+
+int launch_apply_rgba_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
+                                  const uint8_t *d_lut)
+{
+    return launch_fb_bilinear(ctx, plates, pitches, dst, dst_pitch, d_lut, false);
+}
+
+// ... with the positions outside a pixel's plate resolved through ctx->d_seam, which the caller has made current
+int launch_apply_rgba_fb_bilinear_seams(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst,
+                                        int dst_pitch, const uint8_t *d_lut)
+{
+    if (!ctx->d_seam || !ctx->d_seam_current || ctx->seam_table.size() != (size_t)BK_MAX_PLATES * 4u * ((size_t)ctx->ps + 2u))
+        return ctx->fail(BK_E_STATE, "bk_apply_rgba_fb_bilinear_seams_device: the seam table on the device is not the current one");
+    return launch_fb_bilinear(ctx, plates, pitches, dst, dst_pitch, d_lut, true);
 }

@@ -1139,6 +1139,57 @@ extern "C" int bk_debug_forward_tiles(bk_ctx *ctx, int *taken, int *total)
 }
 #endif
 
+// ---- the seam table (bk_read_seam_table, bk_apply_rgba_fb_bilinear_seams_device) ---------------------------------------------
+/* One entry: the texel that stands in for the VIRTUAL texel (x, y) one step outside plate p (x or y is -1 or ps), in the reference
+ * layout, or NULL.  The ray through the virtual texel's centre (plate_uv_to_ray, fisheye.c:1198), the plate it selects
+ * (ray_to_plate_index, :2023-2050 - the globe's globe_plate where there is one), then set_lensmap_from_ray's position on that plate
+ * exactly as bk_inverse_entry / h_inverse_entry take it from the float ray on (:2055-2062, :2065, :1988, :1971).  No grid, no tint. */
+static uint32_t seam_entry(bk_ctx *ctx, HostEval &E, const BkBuildParams &bp, int p, int x, int y)
+{
+    const double u = ((double)x + 0.5) / bp.ps, v = ((double)y + 0.5) / bp.ps;
+    float ray[3];
+    bk::h_plate_uv_to_ray(ctx->plates[p], u, v, ray);
+    const int q = h_ray_to_plate_index(E, bp, ray);
+    if (q < 0 || q == p) return BK_NULL_OFFSET;
+    const BkPlateDev &t = bp.plates[q];
+    const double px_ = (double)h_dot3(t.right, ray), py_ = (double)h_dot3(t.up, ray), pz_ = (double)h_dot3(t.forward, ray);
+    const double tu = px_ / pz_ * t.dist64 + 0.5, tv = -py_ / pz_ * t.dist64 + 0.5;
+    if (!(tu >= 0 && tu <= 1 && tv >= 0 && tv <= 1)) return BK_NULL_OFFSET;
+    const int tx = h_trunc_to_int(tu * bp.ps), ty = h_trunc_to_int(tv * bp.ps);
+    if (!(tx >= 0 && tx < bp.ps && ty >= 0 && ty < bp.ps)) return BK_NULL_OFFSET;
+    return (uint32_t)q * (uint32_t)(bp.ps * bp.ps) + (uint32_t)ty * (uint32_t)bp.ps + (uint32_t)tx;
+}
+
+/* uint32 [6][4][ps + 2]: edge 0 = row y = -1, 1 = row y = ps, 2 = column x = -1, 3 = column x = ps; index = the coordinate along the
+ * edge + 1 (0 and ps + 1: the corners, in both edges that meet there).  Plates from numplates on: NULL.  Without a globe_plate callback
+ * every step is an IEEE operation; with one the interpreter answers on the host's libm, as it does for flagged pixels (copies of its
+ * state on the pool's workers: the context's own is left as it is). */
+int bk::seam_table_compute(bk_ctx *ctx, std::vector<uint32_t> &out)
+{
+    LensProgram *P = bk::prog_of(ctx);
+    BkBuildParams bp;
+    fill_params(ctx, &bp);
+    const int ps = ctx->ps, n1 = ps + 2;
+    out.assign((size_t)BK_MAX_PLATES * 4 * n1, BK_NULL_OFFSET);
+    const size_t n = (size_t)ctx->numplates * 4 * n1;
+    auto one = [&](HostEval &E, size_t k) {
+        const int p = (int)(k / (size_t)(4 * n1)), edge = (int)(k / (size_t)n1) & 3, along = (int)(k % (size_t)n1) - 1;
+        const int x = edge == 2 ? -1 : edge == 3 ? ps : along, y = edge == 0 ? -1 : edge == 1 ? ps : along;
+        out[k] = seam_entry(ctx, E, bp, p, x, y);
+    };
+    if (!P->globe_plate.is_function()) {
+        HostEval E{nullptr, Value(), Value(), Value()};
+        for (size_t k = 0; k < n; ++k) one(E, k);
+        return BK_OK;
+    }
+    try {
+        for_each_flagged(P, n, one);
+    } catch (const LuaError &e) {
+        return ctx->fail(BK_E_SCRIPT, "seam table: %s", e.what());
+    }
+    return BK_OK;
+}
+
 #if BK_DEBUG_API
 /* test hook: the kernel-argument block bk_build would launch with (calc_zoom done, device pointers as they are -
  * null on a BK_DEVICE_NONE context).  tests/hostemu compiles the generated translation unit for the host and runs it

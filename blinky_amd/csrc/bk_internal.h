@@ -99,6 +99,16 @@ struct bk_ctx {
     // subtexel_valid: it describes the lensmap in place (lives and dies with lensmap_valid)
     uint16_t *d_subtexel = nullptr;
     bool subtexel_on = false, subtexel_valid = false;
+    // the seam table (bk_read_seam_table / bk_set_seam_table / bk_apply_rgba_fb_bilinear_seams_device): uint32 [6][4][ps + 2] in the
+    // reference layout, the texels that stand in for the virtual ones a step outside every plate.  Made on the host on first use
+    // (bk::seam_table_ready) or set by the caller (seam_user), never by a build; dropped (bk::seam_drop) by whatever can change the
+    // plates, the platesize or the globe_plate root.  d_seam = its decoded device form, uint2 [6][4][ps + 2] = {plate * gp * ph or
+    // 0xFFFFFFFF, py << 16 | px}, uploaded once per table (d_seam_current) into a buffer of d_seam_words entries
+    std::vector<uint32_t> seam_table;
+    bool seam_valid = false, seam_user = false;
+    uint2 *d_seam = nullptr;
+    size_t d_seam_words = 0;
+    bool d_seam_current = false;
     uint8_t *d_frame = nullptr;      // [row1-row0][W] staging for bk_apply (host dst)
     uint8_t *d_pal = nullptr;        // [6][256]
     uint8_t *d_lut_rgba = nullptr;   // [4][6][256] the byte LUTs of bk_apply_rgba_tinted_device; a buffer of its own (d_pal stays the 8-bit palette), allocated on first use
@@ -255,6 +265,9 @@ int launch_apply_rgba_fb(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], c
 // the same frame with every pixel blended from the four texels around its sub-texel position (ctx->d_subtexel, which must be there)
 int launch_apply_rgba_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
                                   const uint8_t *d_lut);
+// ... with the four positions resolved one by one: those outside the plate through ctx->d_seam (which must be current)
+int launch_apply_rgba_fb_bilinear_seams(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst,
+                                        int dst_pitch, const uint8_t *d_lut);
 int coopmap_stats(bk_ctx *ctx, int out[6]);   // blocks, direct-gather blocks, empty blocks, LDS bytes per buffer
 int coopmap_traffic_model(bk_ctx *ctx, uint64_t out[8]);
 int coopmap_xcd_probe(bk_ctx *ctx, int *out, int nwg);
@@ -288,5 +301,10 @@ void lensprogram_free(LensProgram *);
 int build_module_ready(bk_ctx *ctx);
 // bk_api.cpp
 void empty_context(bk_ctx *ctx);
+// the seam table: forget it (a caller-set one too); make sure ctx->seam_table is there (who = the caller's name for messages)
+inline void seam_drop(bk_ctx *ctx) { ctx->seam_valid = ctx->seam_user = ctx->d_seam_current = false; }
+int seam_table_ready(bk_ctx *ctx, const char *who);
+// bk_build.cpp: the table for the globe and platesize in place, uint32 [6][4][ps + 2], on the host
+int seam_table_compute(bk_ctx *ctx, std::vector<uint32_t> &out);
 
 }  // namespace bk

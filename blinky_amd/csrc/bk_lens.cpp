@@ -104,6 +104,7 @@ extern "C" int bk_load_globe(bk_ctx *ctx, const char *src, size_t len, const cha
     ctx->numplates = 0;
     ctx->globe_valid = false;
     ctx->clear_debug_corners();                       // (a test's corner table was sized for the plates that are going)
+    bk::seam_drop(ctx);                               // (the seam table was made for them, or set for them)
     P->globe_plate = Value();
     try {
         I.run(std::string(src, len), name);
@@ -165,6 +166,7 @@ extern "C" int bk_set_globe_plates(bk_ctx *ctx, const bk_plate *plates, int nump
     ctx->numplates = numplates;
     ctx->globe_valid = true;
     ctx->clear_debug_corners();
+    bk::seam_drop(ctx);
     if (ctx->prog) { ctx->prog->globe_plate = Value(); bk::roots_changed(ctx->prog); }
     return BK_OK;
 }
@@ -177,6 +179,7 @@ extern "C" int bk_load_lens(bk_ctx *ctx, const char *src, size_t len, const char
     LensProgram *P = bk::prog_of(ctx);
     Interp &I = P->interp;
     const std::string name = chunkname ? chunkname : "lens";
+    bk::seam_drop(ctx);                               // (globe and lens share one interpreter state: what globe_plate reads may change)
     // LUA_clear_lens, fisheye.c:1880-1894
     for (const char *g : {"map", "max_fov", "max_vfov", "lens_width", "lens_height", "lens_inverse", "lens_forward", "onload"})
         I.set_global(g, Value());
@@ -221,6 +224,7 @@ extern "C" int bk_load_lens(bk_ctx *ctx, const char *src, size_t len, const char
 extern "C" int bk_clear_lens(bk_ctx *ctx)
 {
     if (!ctx) return BK_E_INVALID;
+    bk::seam_drop(ctx);
     if (ctx->prog) { ctx->prog->lens_valid = false; ctx->prog->lens_inverse = ctx->prog->lens_forward = Value(); bk::roots_changed(ctx->prog); }
     return BK_OK;
 }
@@ -230,6 +234,7 @@ extern "C" int bk_clear_globe(bk_ctx *ctx)
     if (!ctx) return BK_E_INVALID;
     ctx->globe_valid = false;
     ctx->numplates = 0;
+    bk::seam_drop(ctx);
     if (ctx->prog) { ctx->prog->globe_plate = Value(); bk::roots_changed(ctx->prog); }
     return BK_OK;
 }

@@ -86,6 +86,9 @@ _SIGS = {
     "bk_apply_rgba_ss2_device": (_i, [_vp, _i, _i, _vp, _i, _sz, _i, _i, _vp]),
     "bk_apply_rgba_fb_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp, _i]),
     "bk_apply_rgba_fb_bilinear_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp]),
+    "bk_apply_rgba_fb_bilinear_seams_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp]),
+    "bk_read_seam_table": (_i, [_vp, _vp]),
+    "bk_set_seam_table": (_i, [_vp, _vp]),
     "bk_debug_fb_decode_check": (C.c_longlong, [_i, _i]),
     "bk_globe_device_ptr": (_vp, [_vp, _i]),
     "bk_fill_plate_lcg": (_i, [_vp, _i, _i, C.c_uint32]),
@@ -558,6 +561,37 @@ class Context:
             if lut.shape != (4, MAX_PLATES, 256):
                 raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
         self._chk(lib.bk_apply_rgba_fb_bilinear_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut)))
+
+    def apply_rgba_fb_bilinear_seams_device(self, plates, pitches, dst_ptr, dst_pitch, x0=0, y0=0, lut=None):
+        """apply_rgba_fb_bilinear_device that filters ACROSS plate seams: each of the four positions is resolved on its own, one outside
+        the pixel's plate through the seam table (read_seam_table / set_seam_table); a NULL entry, or one into a plate passed as None,
+        clamps as apply_rgba_fb_bilinear_device does.  All four texels go through the pixel's tint"""
+        if len(plates) != MAX_PLATES or len(pitches) != MAX_PLATES:
+            raise ValueError(f"plates and pitches must have {MAX_PLATES} entries")
+        pp = (_vp * MAX_PLATES)(*[p.value if isinstance(p, C.c_void_p) else p for p in plates])
+        pi = (_i * MAX_PLATES)(*[int(p) for p in pitches])
+        if lut is not None:
+            lut = np.ascontiguousarray(lut, dtype=np.uint8)
+            if lut.shape != (4, MAX_PLATES, 256):
+                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        self._chk(lib.bk_apply_rgba_fb_bilinear_seams_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut)))
+
+    def read_seam_table(self):
+        """uint32 [6][4][ps + 2], reference layout, 0xFFFFFFFF = none: the texel that stands in for the virtual texel one step outside plate
+        p - edge 0: row y = -1, 1: row y = ps, 2: column x = -1, 3: column x = ps; index = the coordinate along the edge + 1 (0 and
+        ps + 1 are the corners).  Made on first use; works without a device"""
+        w, h, ps, r0, r1 = self.size()
+        out = np.empty((MAX_PLATES, 4, ps + 2), np.uint32)
+        self._chk(lib.bk_read_seam_table(self._h, _ptr(out)))
+        return out
+
+    def set_seam_table(self, table):
+        """replace the seam table (a caller's own adjacency); dropped again by whatever changes the globe, the lens or the size"""
+        w, h, ps, r0, r1 = self.size()
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        if table.size != MAX_PLATES * 4 * (ps + 2):
+            raise ValueError(f"table must be uint32 [{MAX_PLATES}][4][{ps + 2}], not {table.shape}")
+        self._chk(lib.bk_set_seam_table(self._h, _ptr(table)))
 
     # ---- the resident single-frame apply (bk_apply_resident_*): one kernel stays on the device, frames are commands
     def resident_begin(self, rubix_on=False, pal=None, idle_ms=0.0):

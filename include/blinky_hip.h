@@ -407,6 +407,48 @@ int bk_apply_rgba_fb_bilinear_device(bk_ctx *ctx, const void *const plates_dev[B
                                      void *dst_dev, int dst_pitch, int x0, int y0,
                                      const uint8_t lut[4][BK_MAX_PLATES][256] /* nullable: NULL = plain, else tinted */);
 
+/* THE SEAM TABLE: which texel lies one step OUTSIDE each of a plate's four edges - what bk_apply_rgba_fb_bilinear_seams_device blends
+ * with at a plate's rim.  Context state of its own, a function of the globe (plates, globe_plate) and the platesize alone: lens, lensmap
+ * and owned rows play no part, nor do the rubix grid and tints.
+ * Layout: uint32 [6][4][ps + 2] in the reference layout (plate * ps * ps + py * ps + px), 0xFFFFFFFF = "no neighbour: clamp".  For plate p,
+ * edge 0 is the row of virtual texels y = -1, edge 1 the row y = ps, edge 2 the column x = -1, edge 3 the column x = ps; index i is the
+ * coordinate along the edge + 1, so i = 0 and i = ps + 1 are the corners, each in two edges with the same value.  Plates at or beyond
+ * the globe's number are all NULL.
+ * Definition, virtual texel (x, y) of plate p: ray = plate_uv_to_ray(p, (x + 0.5) / ps, (y + 0.5) / ps) (fisheye.c:1198);
+ * q = ray_to_plate_index(ray) (:2023-2050; a globe_plate callback is evaluated by the library's interpreter on the host, as flagged pixels
+ * are); q < 0 or q == p: NULL; else the position on q as the inverse build takes it from the float ray on (:2055-2062, the range test
+ * :2065, trunc(u * ps) :1988, the texel test :1971 - a failed test: NULL) and the entry is q * ps * ps + py * ps + px.  Without a callback
+ * every step is an IEEE float / double operation.
+ * Life: computed on the host on first use (the first seam-aware apply or bk_read_seam_table), uploaded once, kept; bk_build never makes it.
+ * Dropped - a caller-set table too - by bk_load_globe, bk_set_globe_plates, bk_clear_globe, bk_load_lens, bk_clear_lens (globe and lens
+ * share one interpreter state) and a bk_resize that changes the size; bk_set_rows and bk_build leave it alone.
+ * bk_read_seam_table copies out 6 * 4 * (ps + 2) words, computing the table if needed; works on a BK_DEVICE_NONE context; BK_E_STATE
+ * without a valid globe or a size.  bk_set_seam_table replaces it (the counterpart of bk_set_lensmap_subtexel: a caller's own adjacency,
+ * tests): BK_E_INVALID for an entry that is neither NULL nor below 6 * ps * ps and for a corner whose two copies differ. */
+int bk_read_seam_table(bk_ctx *ctx, uint32_t *out);
+int bk_set_seam_table(bk_ctx *ctx, const uint32_t *table);
+/* bk_apply_rgba_fb_bilinear_seams_device: bk_apply_rgba_fb_bilinear_device that filters across plate seams.  Arguments, sources,
+ * destination, alignment classes, origin, owned rows, untouched unmapped pixels and errors are that call's; in addition BK_E_STATE when
+ * the seam table cannot be made (no valid globe).
+ * Semantics per mapped pixel: xa, xb, ya, yb, fx, fy as there, BEFORE clamping; each of the four positions (xn, yn) is resolved on its own.
+ * One inside [0, ps - 1]^2 is the own plate's texel.  One outside takes the seam table's entry E of the pixel's plate for that virtual
+ * texel (the corner entry when both coordinates are outside): E NULL, or E's plate passed as a NULL pointer, gives the clamped own-plate
+ * texel of bk_apply_rgba_fb_bilinear_device; otherwise the position is texel E.  Blend and rounding are unchanged.  lut given: all four
+ * texels go through the PIXEL's tint, wherever they came from.
+ * Hence: an all-NULL table gives bk_apply_rgba_fb_bilinear_device's frame byte for byte; a plane of 0x8080 gives
+ * bk_apply_rgba_fb_device's frame byte for byte whatever the table holds (weight-0 neighbours are still read); with all six plates given,
+ * stripe contexts stitch to the single-context frame.
+ * THE CONTRACT ON READS, restated: texels within one texel of a named texel, clamped to the plate, may be read; for a named texel on a
+ * plate's first or last row or column, the table's targets of its virtual neighbours may be read too - a renderer that scissors gets
+ * the targets from bk_read_seam_table.  A plate with an empty footprint may still be NULL: entries into it clamp.
+ * The first call after the table was made, dropped or set (bk_set_seam_table) uploads it: that call allocates, copies from pageable host
+ * memory and WAITS for the context's stream - it blocks the host once per table and must not be made during stream capture; make one
+ * call before capturing.  Later calls only launch.
+ * Measured: tools/bench_rgba.py --fb --bilinear --seams [--tint]. */
+int bk_apply_rgba_fb_bilinear_seams_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
+                                           void *dst_dev, int dst_pitch, int x0, int y0,
+                                           const uint8_t lut[4][BK_MAX_PLATES][256] /* nullable: NULL = plain, else tinted */);
+
 /* ---- resident single-frame apply ------------------------------------------------------------------------------------
  * replaces: the per-frame call of render_lensmap (fisheye.c:803 -> 2406-2424) for hosts whose globes stay in device memory.
  * One bk_apply_device launch per frame re-reads the whole block map of the staged apply (2 bytes per pixel and more: half of a

@@ -7,7 +7,7 @@ At 3840x2160 cube/panini and cube/hammer, over the 64-slot LCG ring of the bench
 B's output is compared with A's plane by plane before anything is timed.  Timing: HIP events on the context's stream, warm-up
 launches first, regions of at least --region seconds made of ten event-timed trains of launches (a region's figure is the median
 train), A / B / A / B ... alternated --repeats times inside this one process.  The target: B's median <= A's median + A's own spread
-(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2] [--upload] [--fb [--bilinear]]
+(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2] [--upload] [--fb [--bilinear [--seams]]]
 
 --tint: the same protocol for f_rubix on truecolour frames, three launches alternated A' / B' / B:
   A'  one bk_apply_device launch of 64 8-bit frames with rubix_on = 1 (existing code: the same bytes through the same number of LUT
@@ -42,6 +42,10 @@ truecolour globes.  --repeats blocks of --reps frames each way; a figure is the 
 The expectation: D < B + P by more than the two spreads together; D against P alone is printed beside it (what a caller whose globes
 stay resident would pay).
 
+--fb --bilinear --seams [--tint] [--reps 31]: L (bk_apply_rgba_fb_bilinear_device, its kernel unchanged) against S
+  (bk_apply_rgba_fb_bilinear_seams_device with the cube's computed seam table), alternated frame by frame as below; S is held to the numpy
+  model (tests/seam_model.py) at full size before anything is timed; the target is S <= L + the two spreads.  Also: the host cost of making
+  the seam table at this platesize, without and with a globe_plate callback.
 --fb --bilinear [--tint] [--reps 31]: bilinear texel filtering against the nearest-texel launch it extends, alternated frame by frame:
   D  bk_apply_rgba_fb_device (--tint: with the tables) - existing code
   L  bk_apply_rgba_fb_bilinear_device from the same plates through the sub-texel plane the build kept (bk_set_subtexel)
@@ -531,6 +535,123 @@ def measure_fb_bilinear(lens, repeats, reps, tint):
                 build_spread_ms={n: max(v) - min(v) for n, v in build_ms.items()})
 
 
+def seam_table_host_ms(globe, repeats=3):
+    """wall ms of making the seam table at 4K's platesize on the host (a device-less context), best of `repeats`"""
+    import time
+    best = None
+    for _ in range(repeats):
+        ctx = blinky_amd.Context(blinky_amd.ffi.DEVICE_NONE)
+        ctx.load_globe(S.script("globes", globe), globe + ".lua")
+        ctx.resize(W, H)
+        t0 = time.perf_counter()
+        ctx.read_seam_table()
+        ms = (time.perf_counter() - t0) * 1e3
+        ctx.close()
+        best = ms if best is None else min(best, ms)
+    return best
+
+
+def measure_fb_seams(lens, repeats, reps, tint):
+    """L (bk_apply_rgba_fb_bilinear_device) against S (bk_apply_rgba_fb_bilinear_seams_device, the cube's computed seam table), frame by
+    frame, from the ring of measure_fb"""
+    import seam_model as M
+    SETS = SLOTS // 4
+    ctx = blinky_amd.Context(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_frames(1)
+    ctx.set_subtexel(True)
+    S.configure(ctx, "cube", lens, None, (W, H))
+    display, _ = ctx.build()
+    ps = min(W, H)
+    shown = [p for p in range(6) if p < len(display) and display[p]]
+    given = tuple(p in shown for p in range(6))
+    lut = None
+    if tint:
+        pal = blinky_amd.ffi.create_palmap(((np.arange(768) * 37) % 256).astype(np.uint8))
+        lut = np.ascontiguousarray(np.broadcast_to(pal, (4, 6, 256)))
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    src = [[torch.randint(0, 256, (ps, ps, 4), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(6)] for _ in range(SETS)]
+    pitch = 4 * ps
+    ptrs = [[src[s][p].data_ptr() if p in shown else None for p in range(6)] for s in range(SETS)]
+    pitches = [pitch] * 6
+    out = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")
+    plug = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+
+    def bilinear(s):
+        ctx.apply_rgba_fb_bilinear_device(ptrs[s], pitches, out.data_ptr(), 4 * W, lut=lut)
+
+    def seams(s):
+        ctx.apply_rgba_fb_bilinear_seams_device(ptrs[s], pitches, out.data_ptr(), 4 * W, lut=lut)
+
+    # before anything is timed: S's frame is the numpy model's, at full size, in the flavour that is timed
+    off, tints = ctx.read_lensmap()
+    sub = ctx.read_subtexel()
+    table = ctx.read_seam_table()
+    plates = np.stack([src[0][p].cpu().numpy() for p in range(6)])
+    seams(0)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy().reshape(H, 4 * W)
+    want = np.zeros((H, 4 * W), np.uint8)
+    for r0 in range(0, H, 120):
+        M.seam_frame(plates, off.reshape(-1), sub, tints.reshape(-1), W, H, ps, (r0, min(H, r0 + 120)), lut, want, 0, 0, table, given)
+    if not np.array_equal(got, want):
+        raise SystemExit(f"{lens}: the seam frame differs from the numpy model in {int((got != want).sum())} bytes - nothing timed")
+    mapped = int((off != 0xFFFFFFFF).sum())
+    rim = 0
+    for r0 in range(0, H, 120):                            # (in bands, as the model above: positions keeps a dozen int64 arrays)
+        band = slice(r0 * W, min(H, r0 + 120) * W)
+        o_band = off.reshape(-1)[band]
+        rim += int((M.positions(o_band, sub[band], ps, table, given)[3].any(0) & (o_band != 0xFFFFFFFF)).sum())
+    del off, tints, sub, plates, got, want
+    for k in range(2 * SETS):
+        (seams if k % 2 else bilinear)(k % SETS)
+    torch.cuda.synchronize()
+    blocks = {"l": [], "s": []}
+    k = 0
+    for _ in range(repeats):
+        ev = []
+        for r in range(2 * reps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            plug.fill_(r & 255)
+            e[0].record(stream)
+            (seams if r % 2 else bilinear)(k % SETS)
+            e[1].record(stream)
+            ev.append(e)
+            k += 1
+        torch.cuda.synchronize()
+        blocks["l"].append(statistics.median(e[0].elapsed_time(e[1]) * 1e3 for e in ev[0::2]))
+        blocks["s"].append(statistics.median(e[0].elapsed_time(e[1]) * 1e3 for e in ev[1::2]))
+    ctx.close()
+    med = {n: statistics.median(v) for n, v in blocks.items()}
+    spread = {n: max(v) - min(v) for n, v in blocks.items()}
+    return dict(lens=lens, W=W, H=H, ps=ps, tint=bool(tint), seams=True, displayed_plates=shown, frames_per_block=reps, blocks=repeats,
+                mapped_pixels=mapped, pixels_resolved_through_the_table=rim, blocks_us=blocks, median_us=med, spread_us=spread,
+                s_over_l=med["s"] / med["l"], target_met=bool(med["s"] <= med["l"] + spread["l"] + spread["s"]))
+
+
+def main_fb_seams(args):
+    rows = []
+    what = "tinted" if args.tint else "plain"
+    for lens in args.lenses.split(","):
+        r = measure_fb_seams(lens, args.repeats, max(31, args.reps), args.tint)
+        rows.append(r)
+        m, s, b = r["median_us"], r["spread_us"], r["blocks_us"]
+        print(f"4K cube/{lens}, one {what} truecolour frame per call from device plates (a ring of 16 sets), plates {r['displayed_plates']} displayed, "
+              f"{r['mapped_pixels']} mapped pixels of which {r['pixels_resolved_through_the_table']} take a texel through the seam table, "
+              f"{r['blocks']} blocks of {r['frames_per_block']} frames each way, L / S alternated:\n"
+              f"  L  bk_apply_rgba_fb_bilinear_device        {m['l']:8.1f} us (blocks {fmt(b['l'])}; spread {s['l']:.1f})\n"
+              f"  S  bk_apply_rgba_fb_bilinear_seams_device  {m['s']:8.1f} us (blocks {fmt(b['s'])}; spread {s['s']:.1f})\n"
+              f"  S == the numpy model at full size; S / L = {r['s_over_l']:.3f}; S <= L + both spreads: {'met' if r['target_met'] else 'MISSED'}", flush=True)
+    host = {g: seam_table_host_ms(g) for g in ("cube", "fast")}
+    print(f"the seam table on the host at platesize {min(W, H)}: cube (no callback) {host['cube']:.2f} ms, fast (globe_plate callback) {host['fast']:.2f} ms", flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+            f.write(json.dumps(dict(seam_table_host_ms=host)) + "\n")
+
+
 def main_fb_bilinear(args):
     rows = []
     what = "tinted" if args.tint else "plain"
@@ -644,11 +765,16 @@ def main():
     ap.add_argument("--ss2", action="store_true", help="2x2 supersampling: full-size truecolour launch A (with --tint: the tinted one) / fused ss2 launch B")
     ap.add_argument("--upload", action="store_true", help="the per-frame loop: full plate uploads A / footprint uploads B / the one-frame apply P behind them")
     ap.add_argument("--fb", action="store_true", help="one frame per call: footprint uploads + the staged one-frame apply B + P / bk_apply_rgba_fb_device D (with --tint / --ss2: the matching pairs)")
+    ap.add_argument("--seams", action="store_true", help="with --fb --bilinear: bk_apply_rgba_fb_bilinear_device L / bk_apply_rgba_fb_bilinear_seams_device S, and the host cost of the seam table")
     ap.add_argument("--bilinear", action="store_true", help="with --fb: bk_apply_rgba_fb_device D / bk_apply_rgba_fb_bilinear_device L (with --tint: both through the tables), and bk_build with the sub-texel plane off / on")
     ap.add_argument("--reps", type=int, default=31, help="--upload / --fb: frames each way per block (at least 31)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_rgba.py measures on the GPU; there is none here")
+    if args.seams:
+        if not (args.fb and args.bilinear) or args.ss2:
+            raise SystemExit("--seams goes with --fb --bilinear (and not with --ss2)")
+        return main_fb_seams(args)
     if args.bilinear:
         if not args.fb or args.ss2:
             raise SystemExit("--bilinear goes with --fb (and not with --ss2)")
