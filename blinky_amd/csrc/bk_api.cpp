@@ -106,7 +106,7 @@ extern "C" bk_ctx *bk_create(int device)
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->num_cus = prop.multiProcessorCount;
     }
     if (hipSetDevice(device) != hipSuccess ||
-        hipMalloc((void **)&ctx->d_pal, BK_MAX_PLATES * 256) != hipSuccess ||
+        hipMalloc((void **)&ctx->pal.d, BK_MAX_PLATES * 256) != hipSuccess ||
         hipMalloc((void **)&ctx->d_display, 2 * (BK_MAX_PLATES + 3) * sizeof(int)) != hipSuccess) {
         g_create_error = "bk_create: hipSetDevice/hipMalloc failed";
         delete ctx;
@@ -129,7 +129,7 @@ static void free_maps(bk_ctx *ctx)
 {
     hipFree(ctx->d_offsets); ctx->d_offsets = nullptr;
     hipFree(ctx->d_tints); ctx->d_tints = nullptr;
-    hipFree(ctx->d_subtexel); ctx->d_subtexel = nullptr; ctx->subtexel_valid = false;
+    hipFree(ctx->d_subtexel); ctx->d_subtexel = nullptr;
     hipFree(ctx->d_convert); ctx->d_convert = nullptr;
     hipFree(ctx->d_frame); ctx->d_frame = nullptr;
     hipFree(ctx->d_mask); ctx->d_mask = nullptr;
@@ -137,10 +137,7 @@ static void free_maps(bk_ctx *ctx)
     if (ctx->h_mask) hipHostFree(ctx->h_mask);
     ctx->h_frame = nullptr; ctx->h_mask = nullptr;
     ctx->map_px = 0;
-    ctx->lensmap_valid = false;
-    ctx->spans_valid = false;
-    bk::coopmap_invalidate(ctx);
-    bk::footprint_invalidate(ctx);
+    bk::lensmap_dropped(ctx);
 }
 
 extern "C" void bk_destroy(bk_ctx *ctx)
@@ -156,9 +153,9 @@ extern "C" void bk_destroy(bk_ctx *ctx)
     hipFree(ctx->d_plate_stage);
     hipFree(ctx->d_rgba_stage);
     bk::footprint_free(ctx);
-    hipFree(ctx->d_pal);
-    hipFree(ctx->d_lut_rgba);
-    hipFree(ctx->d_lut_fb);
+    ctx->pal.free();
+    ctx->lut_rgba.free();
+    ctx->lut_fb.free();
     hipFree(ctx->d_seam);
     hipFree(ctx->d_display);
     hipFree(ctx->d_flag_list);
@@ -239,10 +236,8 @@ void bk::empty_context(bk_ctx *ctx)
     bk::footprint_free(ctx);
     ctx->W = ctx->H = ctx->ps = ctx->gp = ctx->ph = 0;
     ctx->row0 = ctx->row1 = 0;
-    ctx->lensmap_valid = false;
-    ctx->subtexel_valid = false;
+    bk::lensmap_dropped(ctx);
     bk::seam_drop(ctx);
-    ctx->spans_valid = false;
     ctx->err = msg;
 }
 
@@ -275,10 +270,8 @@ extern "C" int bk_resize(bk_ctx *ctx, int width, int height)
     };
     ctx->W = width; ctx->H = height; ctx->ps = ps; ctx->gp = gp; ctx->ph = ph;
     ctx->row0 = 0; ctx->row1 = height;
-    ctx->lensmap_valid = false;
-    ctx->subtexel_valid = false;
+    bk::lensmap_dropped(ctx);                               // (also when alloc_maps below keeps the buffers: the same pixel count)
     bk::seam_drop(ctx);                                     // (made for the platesize that was; a caller-set one goes with it)
-    bk::footprint_invalidate(ctx);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail_empty(ctx->fail(BK_E_HIP, "bk_resize: hipStreamSynchronize failed"));
     (void)hipFree(ctx->d_plate_stage);
     ctx->d_plate_stage = nullptr;
@@ -304,10 +297,7 @@ extern "C" int bk_set_rows(bk_ctx *ctx, int row0, int row1)
     if (int r = ensure_device(ctx)) return r;
     if (row0 == ctx->row0 && row1 == ctx->row1) return BK_OK;
     ctx->row0 = row0; ctx->row1 = row1;
-    ctx->lensmap_valid = false;
-    ctx->subtexel_valid = false;
-    ctx->spans_valid = false;
-    bk::footprint_invalidate(ctx);
+    bk::lensmap_dropped(ctx);                   // (also when alloc_maps keeps the buffers: a stripe of the same height)
     return alloc_maps(ctx);
 }
 
@@ -458,11 +448,7 @@ extern "C" int bk_set_lensmap(bk_ctx *ctx, const uint32_t *offsets, const uint8_
     if (int r = bk::subtexel_alloc(ctx)) return r;
     if (ctx->d_subtexel) BK_HIP(ctx, hipMemsetAsync(ctx->d_subtexel, 0x80, px * 2, ctx->stream));
     BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->lensmap_valid = true;
-    ctx->subtexel_valid = ctx->d_subtexel != nullptr;
-    ctx->spans_valid = false;
-    bk::coopmap_invalidate(ctx);
-    bk::footprint_invalidate(ctx);
+    bk::lensmap_replaced(ctx);
     return BK_OK;
 }
 
@@ -802,20 +788,25 @@ extern "C" int bk_dev_read(bk_ctx *ctx, void *dst_host, const void *src_dev, siz
 
 // ---- apply ------------------------------------------------------------------------------
 
+int bk::LutCopy::upload(bk_ctx *ctx, const void *src, size_t bytes)
+{
+    if (!d) BK_HIP(ctx, hipMalloc((void **)&d, bytes));
+    if (cached && stream == ctx->stream && memcmp(host, src, bytes) == 0) return BK_OK;
+    cached = false;
+    BK_HIP(ctx, hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    memcpy(host, src, bytes);
+    stream = ctx->stream;
+    cached = true;
+    return BK_OK;
+}
+
 static int upload_pal(bk_ctx *ctx, int rubix_on, const uint8_t pal[BK_MAX_PLATES][256])
 {
     if (!rubix_on) return BK_OK;
     if (!pal) return ctx->fail(BK_E_INVALID, "rubix_on needs the palette LUTs");
     // (r5) the LUTs a caller passes are the same from frame to frame (f_rubix's palettes change with the game's palette, not with the
-    // view): an upload per call was a copy between every two single-frame launches - 2.6 us of a 10 us launch.  The device copy is
-    // kept while the bytes AND the stream are the same (an upload is ordered with the launches of the stream it was issued on only).
-    if (ctx->pal_cached && ctx->pal_stream == ctx->stream && memcmp(ctx->pal_cache, pal, sizeof ctx->pal_cache) == 0) return BK_OK;
-    ctx->pal_cached = false;
-    BK_HIP(ctx, hipMemcpyAsync(ctx->d_pal, pal, BK_MAX_PLATES * 256, hipMemcpyHostToDevice, ctx->stream));
-    memcpy(ctx->pal_cache, pal, sizeof ctx->pal_cache);
-    ctx->pal_stream = ctx->stream;
-    ctx->pal_cached = true;
-    return BK_OK;
+    // view): an upload per call was a copy between every two single-frame launches - 2.6 us of a 10 us launch.  Hence the kept copy.
+    return ctx->pal.upload(ctx, pal, BK_MAX_PLATES * 256);
 }
 
 extern "C" int bk_apply_device(bk_ctx *ctx, int frame0, int nframes, void *dst_dev, int dst_pitch,
@@ -864,29 +855,9 @@ extern "C" int bk_apply_rgba_device(bk_ctx *ctx, int globe0, int nframes, void *
     return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride);
 }
 
-// the device copy of a truecolour launch's byte LUTs, kept as upload_pal keeps the 8-bit palette: while the bytes AND the stream are
-// the same.  The buffer, its cache, stream and flag are the caller's: the staged launches have one set (upload_lut_rgba; ctx->d_pal and its
-// cache stay what the last 8-bit rubix launch made them), bk_apply_rgba_fb_device another (upload_lut_fb), so neither disturbs the other's.
-static int upload_lut(bk_ctx *ctx, const uint8_t lut[4][BK_MAX_PLATES][256], uint8_t **d_lut, uint8_t *cache, hipStream_t *stream, bool *cached)
-{
-    const size_t bytes = 4 * BK_MAX_PLATES * 256;
-    if (!*d_lut) BK_HIP(ctx, hipMalloc((void **)d_lut, bytes));
-    if (*cached && *stream == ctx->stream && memcmp(cache, lut, bytes) == 0) return BK_OK;
-    *cached = false;
-    BK_HIP(ctx, hipMemcpyAsync(*d_lut, lut, bytes, hipMemcpyHostToDevice, ctx->stream));
-    memcpy(cache, lut, bytes);
-    *stream = ctx->stream;
-    *cached = true;
-    return BK_OK;
-}
-static int upload_lut_rgba(bk_ctx *ctx, const uint8_t lut[4][BK_MAX_PLATES][256])
-{
-    return upload_lut(ctx, lut, &ctx->d_lut_rgba, ctx->lut_rgba_cache, &ctx->lut_rgba_stream, &ctx->lut_rgba_cached);
-}
-static int upload_lut_fb(bk_ctx *ctx, const uint8_t lut[4][BK_MAX_PLATES][256])
-{
-    return upload_lut(ctx, lut, &ctx->d_lut_fb, ctx->lut_fb_cache, &ctx->lut_fb_stream, &ctx->lut_fb_cached);
-}
+// the device copy of a truecolour launch's byte LUTs in `copy` - ctx->lut_rgba for the staged launches, ctx->lut_fb for the frame-buffer
+// ones: neither disturbs the other's, nor ctx->pal, which stays what the last 8-bit rubix launch made it
+static int upload_lut(bk_ctx *ctx, bk::LutCopy &copy, const uint8_t lut[4][BK_MAX_PLATES][256]) { return copy.upload(ctx, lut, sizeof copy.host); }
 
 // bk_apply_rgba_device with rubix: byte c of a mapped pixel of tint t < BK_MAX_PLATES leaves as lut[c][t][v]
 extern "C" int bk_apply_rgba_tinted_device(bk_ctx *ctx, int globe0, int nframes, void *dst_dev, int dst_pitch, size_t frame_stride, int x0, int y0,
@@ -896,9 +867,9 @@ extern "C" int bk_apply_rgba_tinted_device(bk_ctx *ctx, int globe0, int nframes,
     if (int r = rgba_apply_args(ctx, "bk_apply_rgba_tinted_device", globe0, nframes, dst_dev, dst_pitch, frame_stride, x0, y0)) return r;
     if (int r = ensure_device(ctx)) return r;
     bk::Range range("bk_apply_rgba_tinted_device");
-    if (int r = upload_lut_rgba(ctx, lut)) return r;
+    if (int r = upload_lut(ctx, ctx->lut_rgba, lut)) return r;
     uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
-    return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride, ctx->d_lut_rgba);
+    return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride, ctx->lut_rgba.d);
 }
 
 // 2x2 supersampling of the truecolour apply: the lensmap is W x H, the frames written are (W + 1) / 2 x (H + 1) / 2, every pixel the
@@ -911,9 +882,9 @@ extern "C" int bk_apply_rgba_ss2_device(bk_ctx *ctx, int globe0, int nframes, vo
     if (int r = ensure_device(ctx)) return r;                // (ends a resident session)
     bk::Range range("bk_apply_rgba_ss2_device");
     if (lut)
-        if (int r = upload_lut_rgba(ctx, lut)) return r;
+        if (int r = upload_lut(ctx, ctx->lut_rgba, lut)) return r;
     uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0 / 2) * dst_pitch + (size_t)x0 * 4;
-    return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride, lut ? ctx->d_lut_rgba : nullptr, true);
+    return bk::launch_apply_rgba(ctx, globe0, nframes, first, dst_pitch, frame_stride, lut ? ctx->lut_rgba.d : nullptr, true);
 }
 
 // ---- truecolour straight from the renderer's frame buffers (bk_apply_rgba_fb.inc) ----------------------------------------------
@@ -941,34 +912,6 @@ static int fb_apply_args(bk_ctx *ctx, const char *who, const void *const plates_
         if (!plates_dev[p] && ctx->fp_summary(p)[0] != 0)
             return ctx->fail(BK_E_INVALID, "%s: plate %d is NULL, but the lensmap reads %d of its tiles (bk_plate_footprint)", who, p, ctx->fp_summary(p)[0]);
     return BK_OK;
-}
-
-// one truecolour frame out of six row-major 32-bit plates in device memory: no ring slot, no block map, either apply variant
-extern "C" int bk_apply_rgba_fb_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES], void *dst_dev,
-                                       int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256], int ss2)
-{
-    static const char *who = "bk_apply_rgba_fb_device";
-    if (int r = fb_apply_args(ctx, who, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, ss2)) return r;
-    bk::Range range(who);
-    if (lut)
-        if (int r = upload_lut_fb(ctx, lut)) return r;
-    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + (ss2 ? ctx->row0 / 2 : ctx->row0)) * dst_pitch + (size_t)x0 * 4;
-    return bk::launch_apply_rgba_fb(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->d_lut_fb : nullptr, ss2 != 0);
-}
-
-// the same frame, every mapped pixel blended from the four texels around where its ray landed (the sub-texel plane of bk_set_subtexel)
-extern "C" int bk_apply_rgba_fb_bilinear_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
-                                                void *dst_dev, int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256])
-{
-    static const char *who = "bk_apply_rgba_fb_bilinear_device";
-    if (int r = fb_apply_args(ctx, who, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, 0)) return r;
-    if (!ctx->subtexel_valid || !ctx->d_subtexel)
-        return ctx->fail(BK_E_STATE, "%s: the lensmap has no sub-texel plane (bk_set_subtexel(ctx, 1), then bk_build / bk_set_lensmap)", who);
-    bk::Range range(who);
-    if (lut)
-        if (int r = upload_lut_fb(ctx, lut)) return r;
-    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
-    return bk::launch_apply_rgba_fb_bilinear(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->d_lut_fb : nullptr);
 }
 
 // ---- the seam table: which texel of which plate lies one step outside every plate's four edges ----------------------------------
@@ -1040,21 +983,45 @@ static int seam_upload(bk_ctx *ctx)
     return BK_OK;
 }
 
+// what the three frame-buffer applies do alike; `who` names the entry point in every message
+static int fb_apply(bk_ctx *ctx, const char *who, bk::FbMode mode, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
+                    void *dst_dev, int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256], int ss2)
+{
+    if (int r = fb_apply_args(ctx, who, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, ss2)) return r;
+    if (ss2) mode = bk::FB_SS2;                              // (bk_apply_rgba_fb_device's argument, checked above; 0 from the others)
+    const bool bilinear = mode == bk::FB_BILINEAR || mode == bk::FB_BILINEAR_SEAMS;
+    if (bilinear && (!ctx->subtexel_valid || !ctx->d_subtexel))
+        return ctx->fail(BK_E_STATE, "%s: the lensmap has no sub-texel plane (bk_set_subtexel(ctx, 1), then bk_build / bk_set_lensmap)", who);
+    if (mode == bk::FB_BILINEAR_SEAMS) {
+        if (int r = bk::seam_table_ready(ctx, who)) return r;
+        if (int r = seam_upload(ctx)) return r;
+    }
+    bk::Range range(who);
+    if (lut)
+        if (int r = upload_lut(ctx, ctx->lut_fb, lut)) return r;
+    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + (ss2 ? ctx->row0 / 2 : ctx->row0)) * dst_pitch + (size_t)x0 * 4;
+    return bk::launch_apply_rgba_fb(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->lut_fb.d : nullptr, mode);
+}
+
+// one truecolour frame out of six row-major 32-bit plates in device memory: no ring slot, no block map, either apply variant
+extern "C" int bk_apply_rgba_fb_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES], void *dst_dev,
+                                       int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256], int ss2)
+{
+    return fb_apply(ctx, "bk_apply_rgba_fb_device", bk::FB_NEAREST, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, lut, ss2);
+}
+
+// the same frame, every mapped pixel blended from the four texels around where its ray landed (the sub-texel plane of bk_set_subtexel)
+extern "C" int bk_apply_rgba_fb_bilinear_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
+                                                void *dst_dev, int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256])
+{
+    return fb_apply(ctx, "bk_apply_rgba_fb_bilinear_device", bk::FB_BILINEAR, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, lut, 0);
+}
+
 // bk_apply_rgba_fb_bilinear_device with each of the four positions resolved on its own: one outside the plate is the seam table's texel
 extern "C" int bk_apply_rgba_fb_bilinear_seams_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
                                                       void *dst_dev, int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256])
 {
-    static const char *who = "bk_apply_rgba_fb_bilinear_seams_device";
-    if (int r = fb_apply_args(ctx, who, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, 0)) return r;
-    if (!ctx->subtexel_valid || !ctx->d_subtexel)
-        return ctx->fail(BK_E_STATE, "%s: the lensmap has no sub-texel plane (bk_set_subtexel(ctx, 1), then bk_build / bk_set_lensmap)", who);
-    if (int r = bk::seam_table_ready(ctx, who)) return r;
-    if (int r = seam_upload(ctx)) return r;
-    bk::Range range(who);
-    if (lut)
-        if (int r = upload_lut_fb(ctx, lut)) return r;
-    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
-    return bk::launch_apply_rgba_fb_bilinear_seams(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->d_lut_fb : nullptr);
+    return fb_apply(ctx, "bk_apply_rgba_fb_bilinear_seams_device", bk::FB_BILINEAR_SEAMS, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, lut, 0);
 }
 
 // ---- resident single-frame apply (bk_apply_resident.inc) ------------------------------------------------------------

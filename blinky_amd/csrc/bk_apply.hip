@@ -342,22 +342,22 @@ int launch_apply(bk_ctx *ctx, int frame0, int nframes, uint8_t *dst, int dst_pit
         if (rubix_on)
             hipLaunchKernelGGL(apply_direct4<true>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets,
                                ctx->d_tints, ctx->d_globe, gstride, ctx->nframes, frame0, dst,
-                               dst_pitch, frame_stride, ctx->W, gpr, ngroups, nframes, fchunk, ctx->d_pal);
+                               dst_pitch, frame_stride, ctx->W, gpr, ngroups, nframes, fchunk, ctx->pal.d);
         else
             hipLaunchKernelGGL(apply_direct4<false>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets,
                                ctx->d_tints, ctx->d_globe, gstride, ctx->nframes, frame0, dst,
-                               dst_pitch, frame_stride, ctx->W, gpr, ngroups, nframes, fchunk, ctx->d_pal);
+                               dst_pitch, frame_stride, ctx->W, gpr, ngroups, nframes, fchunk, ctx->pal.d);
     } else {
         const int npix = ctx->W * rows;
         dim3 grid((npix + 255) / 256, fblocks);
         if (rubix_on)
             hipLaunchKernelGGL(apply_direct1<true>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets,
                                ctx->d_tints, ctx->d_globe, gstride, ctx->nframes, frame0, dst,
-                               dst_pitch, frame_stride, ctx->W, npix, nframes, fchunk, ctx->d_pal);
+                               dst_pitch, frame_stride, ctx->W, npix, nframes, fchunk, ctx->pal.d);
         else
             hipLaunchKernelGGL(apply_direct1<false>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets,
                                ctx->d_tints, ctx->d_globe, gstride, ctx->nframes, frame0, dst,
-                               dst_pitch, frame_stride, ctx->W, npix, nframes, fchunk, ctx->d_pal);
+                               dst_pitch, frame_stride, ctx->W, npix, nframes, fchunk, ctx->pal.d);
     }
     BK_HIP(ctx, hipGetLastError());
     return BK_OK;

@@ -1589,7 +1589,7 @@ static int launch_compiled(bk_ctx *ctx, CoopMap *cm, int frame0, int nframes, ui
     const bool rubix = rubix_on != 0;
     const CoopKernel kernel = cm->rg == 1 ? coop_kernel_of<1>(rubix, once, dma, wideq) : cm->rg == 2 ? coop_kernel_of<2>(rubix, once, dma, wideq)
                                                                                                      : coop_kernel_of<4>(rubix, once, dma, wideq);
-    return coop_launch(kernel, ctx, cm, grid, shmem, ctx->nframes, frame0, nframes, fchunk, lds_buf, dst, dst_pitch, frame_stride, ctx->d_pal, kflags);
+    return coop_launch(kernel, ctx, cm, grid, shmem, ctx->nframes, frame0, nframes, fchunk, lds_buf, dst, dst_pitch, frame_stride, ctx->pal.d, kflags);
 }
 
 // ---------------------------------------------------------------------------------------------

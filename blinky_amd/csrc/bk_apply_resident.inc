@@ -578,7 +578,7 @@ struct Resident {
     ResHost *h = nullptr;              // pinned
     uint32_t *d_ring = nullptr, *d_done = nullptr, *d_up = nullptr;
     int *d_assign = nullptr;           // the plan: every workgroup's blocks
-    uint8_t *d_pal = nullptr;          // the session's OWN copy of the tint LUTs (ctx->d_pal belongs to whoever applied last)
+    uint8_t *d_pal = nullptr;          // the session's OWN copy of the tint LUTs (ctx->pal.d belongs to whoever applied last)
     int *d_phase = nullptr;            // every workgroup's frame phase (frame stride, r5)
     int cap_phase = 0;                 // ints allocated behind d_phase
     int form = 1;
@@ -1147,8 +1147,8 @@ int resident_begin(bk_ctx *ctx, int rubix_on, double idle_ms)
     }
     R->shrink = 0;
     R->rubix = rubix_on != 0;
-    // (fixed for the session, also across a transparent relaunch after somebody else's bk_apply replaced ctx->d_pal)
-    if (R->rubix) BK_HIP(ctx, hipMemcpyAsync(R->d_pal, ctx->d_pal, BK_PAL_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
+    // (fixed for the session, also across a transparent relaunch after somebody else's bk_apply replaced ctx->pal.d)
+    if (R->rubix) BK_HIP(ctx, hipMemcpyAsync(R->d_pal, ctx->pal.d, BK_PAL_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
     if (idle_ms > 0) R->idle_ms = idle_ms;
     R->base += R->next_seq;                    // tickets go on counting
     R->pending.clear();

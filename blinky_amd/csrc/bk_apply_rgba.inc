@@ -485,7 +485,7 @@ int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst, int ds
     const int planes = 4 * nframes;
     const bool rubix = d_lut != nullptr;
     // the plain / the tinted block map, compiled and tuned as for a launch of that many 8-bit frames of that flavour (the tuning launches
-    // of a tinted map are 8-bit rubix launches through whatever ctx->d_pal holds: their output is scratch)
+    // of a tinted map are 8-bit rubix launches through whatever ctx->pal.d holds: their output is scratch)
     if (int r = ensure_coopmap(ctx, planes, rubix ? 1 : 0)) return r;
     CoopMap *cm = ctx->coopmap;
     if (rubix != cm->tinted) return ctx->fail(BK_E_STATE, "truecolour apply: the block map is not of this launch's flavour (internal)");
@@ -507,5 +507,5 @@ int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst, int ds
             : (rubix ? (cm->rg == 1 ? apply_coop_rgba_tinted_kernel<1> : cm->rg == 2 ? apply_coop_rgba_tinted_kernel<2> : apply_coop_rgba_tinted_kernel<4>)
                      : (cm->rg == 1 ? apply_coop_rgba_kernel<1> : cm->rg == 2 ? apply_coop_rgba_kernel<2> : apply_coop_rgba_kernel<4>));
     return coop_launch(kernel, ctx, cm, grid, (size_t)lds_buf + (rubix ? BK_PAL_BYTES : 0), ctx->nframes / 4, globe0, nframes, fchunk, lds_buf, dst,
-                       dst_pitch, frame_stride, rubix ? d_lut : ctx->d_pal, kflags);
+                       dst_pitch, frame_stride, rubix ? d_lut : ctx->pal.d, kflags);
 }

@@ -18,7 +18,7 @@
 // bk_texel_coords on the CPU - every tile of a plate, every plate's boundaries; tests/test_rgba_fb_abi.py runs it for EVERY padded plate
 // width bk_resize accepts, at the largest height it accepts with it.
 // The six pointers and pitches travel by value in the kernel arguments (BkFbPlates) and are picked by the same five comparisons
-// (selects - picked by number, an indexed copy of the struct lives in scratch).
+// (BK_FB_PICK: selects - picked by number, an indexed copy of the struct lives in scratch).
 //
 // Work layout, full size (apply_rgba_fb_kernel<RUBIX>): a workgroup of 256 covers a 128 x 8 patch of the frame - 32 lanes x 4
 // consecutive pixels by 8 rows, a wave two rows - so the source lines the patch touches are shared in the CU's L1 and the XCD's L2.
@@ -97,16 +97,35 @@ struct BkFbGeom {
     int lmap4;                    // W % 4 == 0: a lane's four entries are one aligned 16-byte load, its four tints one dword
 };
 
+// The plate pick, stated once: the plate of device offset `off` (a name or a member: it stands bare below), the plate's base and its
+// pitch out of the BkFbPlates `s` and the BkFbGeom `g` of the function it stands in.  BK_FB_PLATE's five comparisons, kept as they
+// are: they also pick the pointer and the pitch (selects on the comparisons - picked by the plate's NUMBER the compiler makes an
+// indexed copy of the struct in scratch, 80 bytes per lane).
+// A macro, as BK_FB_STORE4 and BK_FB_BILINEAR_AT below: a __forceinline__ function with reference or struct results was tried for each
+// and is the same arithmetic but not the same kernel - other register allocation in all eight, and in the function forms tried together
+// the tinted ss2 kernel at 82 VGPRs for 70.  Expanded in place they are, instruction for instruction, the kernels as they were.
+#define BK_FB_PICK(off, plate, base, pitch)                                                                                        \
+    const bool c1 = off >= g.pb, c2 = off >= 2u * g.pb, c3 = off >= 3u * g.pb, c4 = off >= 4u * g.pb, c5 = off >= 5u * g.pb;       \
+    plate = (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3 + (uint32_t)c4 + (uint32_t)c5;                                              \
+    base = c5 ? s.p[5] : c4 ? s.p[4] : c3 ? s.p[3] : c2 ? s.p[2] : c1 ? s.p[1] : s.p[0];                                           \
+    pitch = c5 ? s.pitch[5] : c4 ? s.pitch[4] : c3 ? s.pitch[3] : c2 ? s.pitch[2] : c1 ? s.pitch[1] : s.pitch[0]
+
+// lensmap entry `off` decoded: its plate's number (returned), base and pitch, the texel's column and row
+__device__ __forceinline__ uint32_t bk_fb_locate(const BkFbPlates &s, const BkFbGeom &g, uint32_t off, const uint8_t *&base, uint32_t &pitch, uint32_t &px,
+                                                 uint32_t &py)
+{
+    uint32_t plate;
+    BK_FB_PICK(off, plate, base, pitch);
+    BK_FB_TEXEL(off - plate * g.pb, g.tpr, g.tpr_m, __umulhi, px, py);
+    return plate;
+}
+
 // where the texel of lensmap entry `off` lies in the caller's plates
 __device__ __forceinline__ const uint32_t *bk_fb_texel(const BkFbPlates &s, const BkFbGeom &g, uint32_t off)
 {
-    // BK_FB_PLATE's five comparisons, kept as they are: they also pick the plate's pointer and pitch (selects on the comparisons; picked
-    // by the plate's number the compiler makes an indexed copy of the struct in scratch, 80 bytes per lane)
-    const bool c1 = off >= g.pb, c2 = off >= 2u * g.pb, c3 = off >= 3u * g.pb, c4 = off >= 4u * g.pb, c5 = off >= 5u * g.pb;
-    const uint32_t plate = (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3 + (uint32_t)c4 + (uint32_t)c5;
-    const uint8_t *base = c5 ? s.p[5] : c4 ? s.p[4] : c3 ? s.p[3] : c2 ? s.p[2] : c1 ? s.p[1] : s.p[0];
-    const uint32_t pitch = c5 ? s.pitch[5] : c4 ? s.pitch[4] : c3 ? s.pitch[3] : c2 ? s.pitch[2] : c1 ? s.pitch[1] : s.pitch[0];
-    uint32_t px, py;
+    const uint8_t *base;
+    uint32_t plate, pitch, px, py;
+    BK_FB_PICK(off, plate, base, pitch);
     BK_FB_TEXEL(off - plate * g.pb, g.tpr, g.tpr_m, __umulhi, px, py);
     return reinterpret_cast<const uint32_t *>(base + (size_t)py * pitch + (size_t)px * 4u);
 }
@@ -163,13 +182,35 @@ __device__ __forceinline__ void bk_fb_load_lut(const uint8_t *__restrict__ lut, 
     __syncthreads();
 }
 
+// a kernel's first statement: the LUTs' place in LDS (16 bytes nobody reads in a plain kernel) and, tinted, the load
+#define BK_FB_LUT_S(lut)                                                                                                           \
+    __shared__ __attribute__((aligned(16))) uint8_t lut_s[RUBIX ? 4 * BK_PAL_BYTES : 16];                                          \
+    if (RUBIX) bk_fb_load_lut(lut, lut_s)
+
+// The store tail: a lane's four pixels v[0..3] to `out`, w0..w3 = pixel k is written: one non-temporal 16-byte store when all four are
+// and the address is 16-byte aligned, a dword store per written pixel otherwise.  `all` is w0 && w1 && w2 && w3 as the kernel has it -
+// the full-size kernels a flag made after `out`, ss2 the expression itself: which of the two, and where, is part of the code that comes
+// out, so each keeps its own.  (A macro for BK_FB_PICK's reason.)
+#define BK_FB_STORE4(out, v, all, w0, w1, w2, w3)                                                                                  \
+    do {                                                                                                                           \
+        if ((all) && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {                                                              \
+            typedef uint32_t v4u __attribute__((ext_vector_type(4)));                                                              \
+            v4u q_ = {(v)[0], (v)[1], (v)[2], (v)[3]};                                                                             \
+            __builtin_nontemporal_store(q_, reinterpret_cast<v4u *>(out));                                                         \
+        } else {                                                                                                                   \
+            if (w0) reinterpret_cast<uint32_t *>(out)[0] = (v)[0];                                                                 \
+            if (w1) reinterpret_cast<uint32_t *>(out)[1] = (v)[1];                                                                 \
+            if (w2) reinterpret_cast<uint32_t *>(out)[2] = (v)[2];                                                                 \
+            if (w3) reinterpret_cast<uint32_t *>(out)[3] = (v)[3];                                                                 \
+        }                                                                                                                          \
+    } while (0)
+
 // dst = pixel (0, 0) of the owned rows' part of the frame (origin applied); grid = (ceil(W / 128), ceil(rows / 8))
 template <bool RUBIX>
 __global__ __launch_bounds__(256) void apply_rgba_fb_kernel(const uint32_t *__restrict__ lmap, const uint8_t *__restrict__ tints, const BkFbPlates src,
                                                             const BkFbGeom g, uint8_t *__restrict__ dst, int dst_pitch, const uint8_t *__restrict__ lut)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut_s[RUBIX ? 4 * BK_PAL_BYTES : 16];
-    if (RUBIX) bk_fb_load_lut(lut, lut_s);
+    BK_FB_LUT_S(lut);
     const int x = (int)blockIdx.x * 128 + (int)(threadIdx.x & 31u) * 4, row = (int)blockIdx.y * 8 + (int)(threadIdx.x >> 5);
     if (row >= g.rows || x >= g.W) return;
     uint32_t o[4], t[4];
@@ -188,15 +229,7 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_kernel(const uint32_t *__re
     }
     uint8_t *out = dst + (size_t)row * dst_pitch + (size_t)x * 4;
     const bool all = o[0] != BK_NULL_OFFSET && o[1] != BK_NULL_OFFSET && o[2] != BK_NULL_OFFSET && o[3] != BK_NULL_OFFSET;      // (entries past W are NULL)
-    if (all && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
-        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-        v4u q = {v[0], v[1], v[2], v[3]};
-        __builtin_nontemporal_store(q, reinterpret_cast<v4u *>(out));
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (o[k] != BK_NULL_OFFSET) reinterpret_cast<uint32_t *>(out)[k] = v[k];
-    }
+    BK_FB_STORE4(out, v, all, o[0] != BK_NULL_OFFSET, o[1] != BK_NULL_OFFSET, o[2] != BK_NULL_OFFSET, o[3] != BK_NULL_OFFSET);
 }
 
 // dst = pixel (0, 0) of the owned rows' part of the HALF-SIZE frame; grid = (ceil(Wo / 128), ceil(rows_o / 8)), Wo = (W + 1) / 2,
@@ -205,8 +238,7 @@ template <bool RUBIX>
 __global__ __launch_bounds__(256) void apply_rgba_fb_ss2_kernel(const uint32_t *__restrict__ lmap, const uint8_t *__restrict__ tints, const BkFbPlates src,
                                                                 const BkFbGeom g, uint8_t *__restrict__ dst, int dst_pitch, const uint8_t *__restrict__ lut)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut_s[RUBIX ? 4 * BK_PAL_BYTES : 16];
-    if (RUBIX) bk_fb_load_lut(lut, lut_s);
+    BK_FB_LUT_S(lut);
     const int xo = (int)blockIdx.x * 128 + (int)(threadIdx.x & 31u) * 4, yo = (int)blockIdx.y * 8 + (int)(threadIdx.x >> 5);
     const int x = 2 * xo, row = 2 * yo;
     if (row >= g.rows || x >= g.W) return;
@@ -253,15 +285,7 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_ss2_kernel(const uint32_t *
         px[j] = lo | (hi << 8);
     }
     uint8_t *out = dst + (size_t)yo * dst_pitch + (size_t)xo * 4;
-    if (n[0] && n[1] && n[2] && n[3] && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {      // (a quad past W has no sample)
-        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-        v4u q = {px[0], px[1], px[2], px[3]};
-        __builtin_nontemporal_store(q, reinterpret_cast<v4u *>(out));
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (n[j]) reinterpret_cast<uint32_t *>(out)[j] = px[j];
-    }
+    BK_FB_STORE4(out, px, n[0] && n[1] && n[2] && n[3], n[0], n[1], n[2], n[3]);      // (a quad past W has no sample)
 }
 
 // ---- BILINEAR (bk_apply_rgba_fb_bilinear_device) ----------------------------------------------------------------------------------
@@ -285,26 +309,34 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_ss2_kernel(const uint32_t *
 // 0.1 % of the pixels take the pass.  What was tried: the pass before the common loads (80 / 84), after them with the decode kept (84 / 90).
 // Measured: tools/bench_rgba.py --fb --bilinear [--seams] [--tint], profiles/rgba_fb_bilinear_apply.txt.
 
-// bk_fb_texel's decode with the parts handed out: the plate's base, its pitch, the texel's column and row (and the plate's number)
-__device__ __forceinline__ uint32_t bk_fb_locate(const BkFbPlates &s, const BkFbGeom &g, uint32_t off, const uint8_t *&base, uint32_t &pitch, uint32_t &px,
-                                                 uint32_t &py)
-{
-    // (selects on the five comparisons, as in bk_fb_texel: picked by the plate's number the struct is copied to scratch)
-    const bool c1 = off >= g.pb, c2 = off >= 2u * g.pb, c3 = off >= 3u * g.pb, c4 = off >= 4u * g.pb, c5 = off >= 5u * g.pb;
-    const uint32_t plate = (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3 + (uint32_t)c4 + (uint32_t)c5;
-    base = c5 ? s.p[5] : c4 ? s.p[4] : c3 ? s.p[3] : c2 ? s.p[2] : c1 ? s.p[1] : s.p[0];
-    pitch = c5 ? s.pitch[5] : c4 ? s.pitch[4] : c3 ? s.pitch[3] : c2 ? s.pitch[2] : c1 ? s.pitch[1] : s.pitch[0];
-    BK_FB_TEXEL(off - plate * g.pb, g.tpr, g.tpr_m, __umulhi, px, py);
-    return plate;
-}
+// The geometry of one bilinear pixel, stated once for the common path and the seams pass: from its entry `off` and its sub `q` (and the
+// kernel's src, g, ps_m1, spare) the weights fx, fy; as locals of the block it stands in `mapped`, the plate's number `plate`, the
+// pair's right column xr = px + (sx >> 8) and lower row yr (the pairs are xr - 1, xr and yr - 1, yr, possibly a step outside the
+// plate); and into a[0..3] the four addresses, row ya | yb, column xa | xb, clamped to the entry's own plate - `spare` all four for an
+// unmapped pixel.  (A macro for BK_FB_PICK's reason.)
+#define BK_FB_BILINEAR_AT(off, q, fx, fy, a)                                                                                       \
+    const bool mapped = (off) != BK_NULL_OFFSET;                                                                                   \
+    const uint8_t *base;                                                                                                           \
+    uint32_t pitch, px, py;                                                                                                        \
+    const uint32_t plate = bk_fb_locate(src, g, (off), base, pitch, px, py);                                                       \
+    const uint32_t sx = ((q) & 255u) + 128u, sy = ((q) >> 8) + 128u;                                                               \
+    (fx) = sx & 255u; (fy) = sy & 255u;                                                                                            \
+    /* the pair px - 1 + (sx >> 8), + 1, clamped to the plate: the left one can only fall below 0, the right one only pass ps - 1 */ \
+    const uint32_t xr = px + (sx >> 8), yr = py + (sy >> 8);                                                                       \
+    const uint32_t xa = xr ? xr - 1u : 0u, ya = yr ? yr - 1u : 0u;                                                                 \
+    const uint32_t xb = xr < ps_m1 ? xr : ps_m1, yb = yr < ps_m1 ? yr : ps_m1;                                                     \
+    const uint8_t *ra = base + (size_t)ya * pitch, *rb = base + (size_t)yb * pitch;                                                \
+    (a)[0] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xa * 4u) : spare;                                            \
+    (a)[1] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xb * 4u) : spare;                                            \
+    (a)[2] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xa * 4u) : spare;                                            \
+    (a)[3] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xb * 4u) : spare
 
 // SEAMS: the four positions of pixel k (a[0..3]: row ya | yb, column xa | xb, already formed clamped to the pixel's own plate) that lie
 // OUTSIDE that plate, through the seam table: seam = uint2 [6][4][n1] {plate * pb or 0xFFFFFFFF, py << 16 | px}, n1 = ps + 2, edge 0 = row -1,
 // 1 = row ps, 2 = column -1, 3 = column ps, index = the coordinate along the edge + 1; a position outside in both axes is the row
 // edge's corner entry.  A NULL entry, or one into a plate passed as NULL, leaves the clamped address.  xr = px + (sx >> 8), yr alike: the
 // pair of columns is xr - 1, xr.  Every lane of the wave issues the four table loads (a lane with nothing outside reads entry 0 and
-// drops it): no load hangs on a divergent branch.  The target's plate arrives as plate * pb and is picked by bk_fb_texel's five comparisons
-// against multiples of pb: selects on the plate's NUMBER become an indexed copy of the struct in scratch.
+// drops it): no load hangs on a divergent branch.  The target's plate arrives as plate * pb, an offset for BK_FB_PICK.
 __device__ __forceinline__ void bk_fb_seam_resolve(const BkFbPlates &s, const BkFbGeom &g, const uint2 *__restrict__ seam, uint32_t n1, bool mapped, uint32_t plate,
                                                    uint32_t xr, uint32_t yr, uint32_t ps_m1, const uint32_t *a[4])
 {
@@ -316,12 +348,12 @@ __device__ __forceinline__ void bk_fb_seam_resolve(const BkFbPlates &s, const Bk
         const bool out = mapped && (ox || oy);
         const uint32_t edge = oy ? jy : 2u + jx, along = oy ? xr + jx : yr + jy;
         const uint2 e = seam[out ? (plate * 4u + edge) * n1 + (along < n1 ? along : n1 - 1u) : 0u];
-        const uint32_t off = e.x;
-        const bool c1 = off >= g.pb, c2 = off >= 2u * g.pb, c3 = off >= 3u * g.pb, c4 = off >= 4u * g.pb, c5 = off >= 5u * g.pb;
-        const uint8_t *base = c5 ? s.p[5] : c4 ? s.p[4] : c3 ? s.p[3] : c2 ? s.p[2] : c1 ? s.p[1] : s.p[0];
-        const uint32_t pitch = c5 ? s.pitch[5] : c4 ? s.pitch[4] : c3 ? s.pitch[3] : c2 ? s.pitch[2] : c1 ? s.pitch[1] : s.pitch[0];
+        const uint8_t *base;
+        uint32_t pitch, target;
+        BK_FB_PICK(e.x, target, base, pitch);
+        (void)target;
         const uint32_t *t = reinterpret_cast<const uint32_t *>(base + (size_t)(e.y >> 16) * pitch + (size_t)(e.y & 0xFFFFu) * 4u);
-        a[j] = out && off != BK_NULL_OFFSET && base ? t : a[j];
+        a[j] = out && e.x != BK_NULL_OFFSET && base ? t : a[j];
         asm volatile("" ::: "memory");
     }
 }
@@ -349,8 +381,7 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint3
                                                                      uint8_t *__restrict__ dst, int dst_pitch, const uint8_t *__restrict__ lut,
                                                                      const uint2 *__restrict__ seam)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut_s[RUBIX ? 4 * BK_PAL_BYTES : 16];
-    if (RUBIX) bk_fb_load_lut(lut, lut_s);
+    BK_FB_LUT_S(lut);
     const int x = (int)blockIdx.x * 128 + (int)(threadIdx.x & 31u) * 4, row = (int)blockIdx.y * 8 + (int)(threadIdx.x >> 5);
     if (row >= g.rows || x >= g.W) return;
     uint32_t o[4], t[4], q[4];
@@ -370,21 +401,8 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint3
     bool rim = false;                                // SEAMS: one of the lane's sixteen positions lies outside its pixel's plate
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const bool mapped = o[k] != BK_NULL_OFFSET;
-        const uint8_t *base;
-        uint32_t pitch, px, py;
-        (void)bk_fb_locate(src, g, o[k], base, pitch, px, py);
-        const uint32_t sx = (q[k] & 255u) + 128u, sy = (q[k] >> 8) + 128u;
-        fx[k] = sx & 255u; fy[k] = sy & 255u;
-        // the pair px - 1 + (sx >> 8), + 1, clamped to the plate: the left one can only fall below 0, the right one only pass ps - 1
-        const uint32_t xr = px + (sx >> 8), yr = py + (sy >> 8);
-        const uint32_t xa = xr ? xr - 1u : 0u, ya = yr ? yr - 1u : 0u;
-        const uint32_t xb = xr < ps_m1 ? xr : ps_m1, yb = yr < ps_m1 ? yr : ps_m1;
-        const uint8_t *ra = base + (size_t)ya * pitch, *rb = base + (size_t)yb * pitch;
-        a[4 * k] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xa * 4u) : spare;
-        a[4 * k + 1] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xb * 4u) : spare;
-        a[4 * k + 2] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xa * 4u) : spare;
-        a[4 * k + 3] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xb * 4u) : spare;
+        BK_FB_BILINEAR_AT(o[k], q[k], fx[k], fy[k], a + 4 * k);
+        (void)plate;
         if (SEAMS) rim |= mapped && (xr == 0u || yr == 0u || xr > ps_m1 || yr > ps_m1);
     }
     uint32_t w[16];
@@ -402,7 +420,7 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint3
     // SEAMS.  Everything up to here is the kernel without it: every pixel blended from its own plate, clamped.  The seam table's dependent
     // loads (entry -> plate base and pitch -> address) are taken only by a wave that has a lane on a rim - one uniform branch, under 1 %
     // of the waves of a 4K frame - and AFTER the common path, when its sixteen addresses and texels are dead: such a wave makes its pixels
-    // again, one at a time, from the entry and the sub (decode, the four clamped addresses, those outside the plate replaced through the
+    // again, one at a time, from the entry and the sub (BK_FB_BILINEAR_AT again, the addresses outside the plate replaced through the
     // table, four loads, tint, blend).  That was meant to keep the pass's registers below the common path's; as built it does not: the
     // kernel takes 68 / 78 VGPRs where the one without SEAMS takes 49 / 66, a wave per SIMD less (the head comment has what it costs).
     // A pixel with nothing outside its plate comes out as it was.
@@ -413,20 +431,9 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint3
             //  alive down to here instead of taking it again: 84 / 90 VGPRs)
             uint32_t ok = o[k], qk = q[k];
             asm volatile("" : "+v"(ok), "+v"(qk));
-            const bool mapped = ok != BK_NULL_OFFSET;
-            const uint8_t *base;
-            uint32_t pitch, px, py;
-            const uint32_t plate = bk_fb_locate(src, g, ok, base, pitch, px, py);
-            const uint32_t sx = (qk & 255u) + 128u, sy = (qk >> 8) + 128u;
-            const uint32_t xr = px + (sx >> 8), yr = py + (sy >> 8);
-            const uint32_t xa = xr ? xr - 1u : 0u, ya = yr ? yr - 1u : 0u;
-            const uint32_t xb = xr < ps_m1 ? xr : ps_m1, yb = yr < ps_m1 ? yr : ps_m1;
-            const uint8_t *ra = base + (size_t)ya * pitch, *rb = base + (size_t)yb * pitch;
+            uint32_t fxk, fyk;
             const uint32_t *b[4];
-            b[0] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xa * 4u) : spare;
-            b[1] = mapped ? reinterpret_cast<const uint32_t *>(ra + (size_t)xb * 4u) : spare;
-            b[2] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xa * 4u) : spare;
-            b[3] = mapped ? reinterpret_cast<const uint32_t *>(rb + (size_t)xb * 4u) : spare;
+            BK_FB_BILINEAR_AT(ok, qk, fxk, fyk, b);
             bk_fb_seam_resolve(src, g, seam, ps_m1 + 3u, mapped, plate, xr, yr, ps_m1, b);
             uint32_t c[4];
 #pragma unroll
@@ -435,59 +442,24 @@ __global__ __launch_bounds__(256) void apply_rgba_fb_bilinear_kernel(const uint3
 #pragma unroll
                 for (int j = 0; j < 4; ++j) c[j] = bk_fb_tint(c[j], t[k], lut_s);
             }
-            v[k] = bk_fb_blend(c[0], c[1], c[2], c[3], sx & 255u, sy & 255u);
+            v[k] = bk_fb_blend(c[0], c[1], c[2], c[3], fxk, fyk);
             asm volatile("" ::: "memory");           // (one pixel at a time: four pixels' table entries and texels in flight are registers)
         }
     }
     uint8_t *out = dst + (size_t)row * dst_pitch + (size_t)x * 4;
     const bool all = o[0] != BK_NULL_OFFSET && o[1] != BK_NULL_OFFSET && o[2] != BK_NULL_OFFSET && o[3] != BK_NULL_OFFSET;      // (entries past W are NULL)
-    if (all && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
-        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-        v4u r = {v[0], v[1], v[2], v[3]};
-        __builtin_nontemporal_store(r, reinterpret_cast<v4u *>(out));
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (o[k] != BK_NULL_OFFSET) reinterpret_cast<uint32_t *>(out)[k] = v[k];
-    }
+    BK_FB_STORE4(out, v, all, o[0] != BK_NULL_OFFSET, o[1] != BK_NULL_OFFSET, o[2] != BK_NULL_OFFSET, o[3] != BK_NULL_OFFSET);
 }
 
-// dst = pixel (x0, y0 + row0) of the frame - ss2: (x0, y0 + row0 / 2) of the half-size frame; plates / pitches: validated by the
-// caller (a NULL plate is one no entry of the owned rows names); d_lut != nullptr: the tinted launch
+// The one launch of this file.  dst = pixel (x0, y0 + row0) of the frame - FB_SS2: (x0, y0 + row0 / 2) of the half-size frame; plates /
+// pitches: validated by the caller (a NULL plate is one no entry of the owned rows names); d_lut != nullptr: the tinted launch.  Both
+// bilinear modes: the caller has made sure of the sub-texel plane; FB_BILINEAR_SEAMS: and has made ctx->d_seam current
 int launch_apply_rgba_fb(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
-                         const uint8_t *d_lut, bool ss2)
+                         const uint8_t *d_lut, FbMode mode)
 {
-    const int rows = ctx->rows();
-    if (rows <= 0 || ctx->W <= 0) return BK_OK;
-    BkFbPlates src;
-    for (int p = 0; p < BK_MAX_PLATES; ++p) {
-        src.p[p] = (const uint8_t *)plates[p];
-        src.pitch[p] = plates[p] ? (uint32_t)pitches[p] : 0u;
-    }
-    BkFbGeom g;
-    g.pb = (uint32_t)ctx->gp * (uint32_t)ctx->ph;
-    g.tpr = (uint32_t)ctx->gp >> 4;
-    g.tpr_m = bk_fb_recip(g.tpr);
-    g.W = ctx->W;
-    g.rows = rows;
-    g.lmap4 = (ctx->W & 3) == 0;
-    const int w = ss2 ? (ctx->W + 1) / 2 : ctx->W, h = ss2 ? (rows + 1) / 2 : rows;
-    const dim3 grid((unsigned)((w + 127) / 128), (unsigned)((h + 7) / 8));
-    if (ss2) {
-        if (d_lut) hipLaunchKernelGGL(apply_rgba_fb_ss2_kernel<true>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, src, g, dst, dst_pitch, d_lut);
-        else hipLaunchKernelGGL(apply_rgba_fb_ss2_kernel<false>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, src, g, dst, dst_pitch, d_lut);
-    } else {
-        if (d_lut) hipLaunchKernelGGL(apply_rgba_fb_kernel<true>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, src, g, dst, dst_pitch, d_lut);
-        else hipLaunchKernelGGL(apply_rgba_fb_kernel<false>, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, src, g, dst, dst_pitch, d_lut);
-    }
-    BK_HIP(ctx, hipGetLastError());
-    return BK_OK;
-}
-
-// dst = pixel (x0, y0 + row0) of the frame; the caller has made sure of the sub-texel plane
-static int launch_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
-                              const uint8_t *d_lut, bool seams)
-{
+    if (mode == FB_BILINEAR_SEAMS &&
+        (!ctx->d_seam || !ctx->d_seam_current || ctx->seam_table.size() != (size_t)BK_MAX_PLATES * 4u * ((size_t)ctx->ps + 2u)))
+        return ctx->fail(BK_E_STATE, "bk_apply_rgba_fb_bilinear_seams_device: the seam table on the device is not the current one");
     const int rows = ctx->rows();
     if (rows <= 0 || ctx->W <= 0) return BK_OK;
     BkFbPlates src;
@@ -503,30 +475,31 @@ static int launch_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATE
     g.rows = rows;
     g.lmap4 = (ctx->W & 3) == 0;
     const uint32_t ps_m1 = (uint32_t)ctx->ps - 1u;
-    const dim3 grid((unsigned)((ctx->W + 127) / 128), (unsigned)((rows + 7) / 8));
-    const uint2 *seam = seams ? ctx->d_seam : nullptr;
-    if (seams) {
-        if (d_lut) hipLaunchKernelGGL((apply_rgba_fb_bilinear_kernel<true, true>), grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut, seam);
-        else hipLaunchKernelGGL((apply_rgba_fb_bilinear_kernel<false, true>), grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut, seam);
-    } else {
-        if (d_lut) hipLaunchKernelGGL((apply_rgba_fb_bilinear_kernel<true, false>), grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut, seam);
-        else hipLaunchKernelGGL((apply_rgba_fb_bilinear_kernel<false, false>), grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch, d_lut, seam);
+    const int w = mode == FB_SS2 ? (ctx->W + 1) / 2 : ctx->W, h = mode == FB_SS2 ? (rows + 1) / 2 : rows;
+    const dim3 grid((unsigned)((w + 127) / 128), (unsigned)((h + 7) / 8));
+    const uint2 *seam = mode == FB_BILINEAR_SEAMS ? ctx->d_seam : nullptr;
+    // the mode's kernel, tinted or plain.  (The cases stand in the order the eight kernels have always been instantiated in: with the
+    // bilinear ones instantiated in another order the compiler allocates the seams kernels' registers differently.)
+#define BK_FB_LAUNCH(tinted, plain, ...)                                                                                           \
+    if (d_lut) hipLaunchKernelGGL(tinted, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, __VA_ARGS__);             \
+    else hipLaunchKernelGGL(plain, grid, dim3(256), 0, ctx->stream, ctx->d_offsets, ctx->d_tints, __VA_ARGS__)
+    switch (mode) {
+    case FB_SS2:
+        BK_FB_LAUNCH(apply_rgba_fb_ss2_kernel<true>, apply_rgba_fb_ss2_kernel<false>, src, g, dst, dst_pitch, d_lut);
+        break;
+    case FB_NEAREST:
+        BK_FB_LAUNCH(apply_rgba_fb_kernel<true>, apply_rgba_fb_kernel<false>, src, g, dst, dst_pitch, d_lut);
+        break;
+    case FB_BILINEAR_SEAMS:
+        BK_FB_LAUNCH((apply_rgba_fb_bilinear_kernel<true, true>), (apply_rgba_fb_bilinear_kernel<false, true>), ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch,
+                     d_lut, seam);
+        break;
+    case FB_BILINEAR:
+        BK_FB_LAUNCH((apply_rgba_fb_bilinear_kernel<true, false>), (apply_rgba_fb_bilinear_kernel<false, false>), ctx->d_subtexel, src, g, ps_m1, dst, dst_pitch,
+                     d_lut, seam);
+        break;
     }
+#undef BK_FB_LAUNCH
     BK_HIP(ctx, hipGetLastError());
     return BK_OK;
-}
-
-int launch_apply_rgba_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
-                                  const uint8_t *d_lut)
-{
-    return launch_fb_bilinear(ctx, plates, pitches, dst, dst_pitch, d_lut, false);
-}
-
-// ... with the positions outside a pixel's plate resolved through ctx->d_seam, which the caller has made current
-int launch_apply_rgba_fb_bilinear_seams(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst,
-                                        int dst_pitch, const uint8_t *d_lut)
-{
-    if (!ctx->d_seam || !ctx->d_seam_current || ctx->seam_table.size() != (size_t)BK_MAX_PLATES * 4u * ((size_t)ctx->ps + 2u))
-        return ctx->fail(BK_E_STATE, "bk_apply_rgba_fb_bilinear_seams_device: the seam table on the device is not the current one");
-    return launch_fb_bilinear(ctx, plates, pitches, dst, dst_pitch, d_lut, true);
 }

@@ -1000,12 +1000,8 @@ extern "C" int bk_build(bk_ctx *ctx, int display_out[BK_MAX_PLATES], double *sca
         ~EmptyUnlessBuilt() { now(); }
     } empty_unless_built{ctx, px};
     BK_HIP(ctx, hipMemsetAsync(ctx->d_display, 0, 2 * kNumCounters * sizeof(int), ctx->stream));      // (two sets of counters: see the forward build)
-    ctx->lensmap_valid = true;
-    ctx->subtexel_valid = ctx->d_subtexel != nullptr;
+    bk::lensmap_replaced(ctx);                        // (here, in front of every way out: whatever the build leaves in the table is new)
     ctx->last_bad_key = 0;
-    ctx->spans_valid = false;
-    bk::coopmap_invalidate(ctx);
-    bk::footprint_invalidate(ctx);                    // (here, in front of every way out: whatever the build leaves in the table is new)
     for (int i = 0; i < BK_MAX_PLATES; ++i) { ctx->display[i] = 0; if (display_out) display_out[i] = 0; }
     ctx->last_build_ms = 0;
     ctx->last_host_eval_ms = ctx->last_kernel_wall_ms = 0;
@@ -1319,9 +1315,7 @@ extern "C" int bk_truncate_build(bk_ctx *ctx, unsigned int bad_key, int display_
     if (bad_key == 0) return BK_OK;
     if (int r = bk::launch_truncate_scan(ctx, bad_key, disp)) return r;
     ctx->last_bad_key = bad_key;
-    ctx->spans_valid = false;
-    bk::coopmap_invalidate(ctx);
-    bk::footprint_invalidate(ctx);
+    bk::lensmap_edited(ctx);                          // (the pass took the plane along where it is valid: its flag stays)
     for (int i = 0; i < BK_MAX_PLATES; ++i) { ctx->display[i] = i < ctx->numplates ? disp[i] : 0; if (display_out) display_out[i] = ctx->display[i]; }
     return BK_OK;
 }

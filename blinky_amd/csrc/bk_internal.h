@@ -41,6 +41,18 @@ struct Span { int row, x0, x1; };
 
 struct Rubix { int numcells = 10; double cell = 4, pad = 1; };   // defaults: fisheye.c:672
 
+// The device copy of a palette or of a truecolour launch's byte LUTs, kept while the bytes AND the stream are the same (an upload is
+// ordered with the launches of the stream it was issued on only).  A context has three, each its own buffer and cache, so that none
+// disturbs another's: the 8-bit palette (bk_apply*), the staged truecolour applies' LUTs, the frame-buffer applies' LUTs.
+struct LutCopy {
+    uint8_t *d = nullptr;                         // allocated by the first upload
+    uint8_t host[4 * BK_MAX_PLATES * 256] = {};   // what d holds, uploaded on `stream` (the palette: the first quarter)
+    hipStream_t stream = nullptr;
+    bool cached = false;
+    int upload(bk_ctx *ctx, const void *src, size_t bytes);      // bk_api.cpp; bytes <= sizeof host, the same for every call
+    void free() { (void)hipFree(d); d = nullptr; cached = false; }
+};
+
 struct LensProgram;   // bk_lens_priv.h: parsed scripts + hiprtc modules
 struct CoopMap;       // bk_apply_coop.hip: per-block staging plans of the workgroup-cooperative apply kernel
 struct Resident;      // bk_apply_resident.inc: the resident single-frame apply (its kernel, command ring and stream)
@@ -110,9 +122,9 @@ struct bk_ctx {
     size_t d_seam_words = 0;
     bool d_seam_current = false;
     uint8_t *d_frame = nullptr;      // [row1-row0][W] staging for bk_apply (host dst)
-    uint8_t *d_pal = nullptr;        // [6][256]
-    uint8_t *d_lut_rgba = nullptr;   // [4][6][256] the byte LUTs of bk_apply_rgba_tinted_device; a buffer of its own (d_pal stays the 8-bit palette), allocated on first use
-    uint8_t *d_lut_fb = nullptr;     // [4][6][256] the byte LUTs of bk_apply_rgba_fb_device: its own buffer and cache (upload_lut_fb), allocated on first use
+    bk::LutCopy pal;                 // [6][256] the 8-bit palette (upload_pal); its buffer is there from bk_create on
+    bk::LutCopy lut_rgba;            // [4][6][256] the byte LUTs of bk_apply_rgba_tinted_device / _ss2_device (pal stays the 8-bit palette)
+    bk::LutCopy lut_fb;              // [4][6][256] the byte LUTs of the frame-buffer applies
     uint64_t *d_mask = nullptr;      // mapped bits, 1 per pixel of the owned rows
     int *d_display = nullptr;        // [6] display flags + [1] error bits + [1] flagged-entry count + [1] first malformed result (scan key + 1) written by the build kernels
     unsigned int last_bad_key = 0;   // of the last bk_build: 1 + scan key of the first pixel whose callback returned a malformed result (0 = none)
@@ -175,15 +187,6 @@ struct bk_ctx {
     int res_part = 0, res_parts = 1, res_reserve = 0;   // bk_set_resident_share: which CUs of every XCD the resident kernel may take
     uint64_t apply_ticket = 0;            // resident mode: the frame bk_apply_begin submitted
     uint8_t res_pal[BK_MAX_PLATES * 256] = {};   // resident mode: the palette the running session was begun with
-    uint8_t pal_cache[BK_MAX_PLATES * 256] = {}; // what d_pal holds, uploaded on pal_stream (upload_pal)
-    hipStream_t pal_stream = nullptr;
-    bool pal_cached = false;
-    uint8_t lut_rgba_cache[4 * BK_MAX_PLATES * 256] = {};   // what d_lut_rgba holds, uploaded on lut_rgba_stream (upload_lut_rgba)
-    hipStream_t lut_rgba_stream = nullptr;
-    bool lut_rgba_cached = false;
-    uint8_t lut_fb_cache[4 * BK_MAX_PLATES * 256] = {};     // what d_lut_fb holds, uploaded on lut_fb_stream
-    hipStream_t lut_fb_stream = nullptr;
-    bool lut_fb_cached = false;
     bool res_rubix = false;
     bool apply_was_resident = false;      // latched by bk_apply_begin: the frame in flight went to the resident kernel
     bk::LensProgram *prog = nullptr;      // owned; freed with bk::lensprogram_free
@@ -251,6 +254,16 @@ int launch_scatter16(bk_ctx *ctx, uint16_t *dst, const uint32_t *h_idx, const ui
 int launch_truncate_scan(bk_ctx *ctx, unsigned int bad_key, int display_out[BK_MAX_PLATES]);
 // bk_apply_coop.hip
 void coopmap_invalidate(bk_ctx *ctx);
+// ---- what follows the lensmap: the sub-texel plane beside it and what is made from its entries on first use - the spans, the block
+// map, the footprint.  Every change of the table goes through one of these three; a new plane or cache joins them here, nowhere else.
+// (coopmap_invalidate ends a resident session and takes a context with no block map, or no device, as it is)
+// the entries in place changed, the plane (if valid) with them: bk_truncate_build, whose pass writes the plane only while it is
+// valid - so the plane's flag is not lensmap_replaced's formula there
+inline void lensmap_edited(bk_ctx *ctx) { ctx->spans_valid = false; coopmap_invalidate(ctx); footprint_invalidate(ctx); }
+// there is no table now (free_maps, empty_context, bk_resize, bk_set_rows): every consumer answers BK_E_STATE until there is one
+inline void lensmap_dropped(bk_ctx *ctx) { ctx->lensmap_valid = ctx->subtexel_valid = false; lensmap_edited(ctx); }
+// the table in place is new (bk_set_lensmap; bk_build, in front of every way out); its plane, where there is one, was written with it
+inline void lensmap_replaced(bk_ctx *ctx) { ctx->lensmap_valid = true; ctx->subtexel_valid = ctx->d_subtexel != nullptr; lensmap_edited(ctx); }
 int launch_apply_coop(bk_ctx *ctx, int frame0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch,
                       size_t frame_stride, int rubix_on);
 // bk_apply_rgba.inc (part of bk_apply_coop.hip): truecolour frames from truecolour globes (four ring slots each);
@@ -259,15 +272,12 @@ int launch_apply_coop(bk_ctx *ctx, int frame0, int nframes, uint8_t *dst_first_o
 int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst_first_owned_row, int dst_pitch, size_t frame_stride,
                       const uint8_t *d_lut = nullptr, bool ss2 = false);
 // bk_apply_rgba_fb.inc (part of bk_apply_coop.hip): one truecolour frame straight out of six row-major 32-bit plates in device memory
-// (a NULL plate: one that no lensmap entry of the owned rows names); dst = the first owned row at the origin; ss2: of the half-size frame
+// (a NULL plate: one that no lensmap entry of the owned rows names); dst = the first owned row at the origin.  FB_SS2: of the half-size
+// frame; FB_BILINEAR: every pixel blended from the four texels around its sub-texel position (ctx->d_subtexel, which must be there);
+// FB_BILINEAR_SEAMS: with the four positions resolved one by one, those outside the plate through ctx->d_seam (which must be current)
+enum FbMode { FB_NEAREST, FB_SS2, FB_BILINEAR, FB_BILINEAR_SEAMS };
 int launch_apply_rgba_fb(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
-                         const uint8_t *d_lut, bool ss2);
-// the same frame with every pixel blended from the four texels around its sub-texel position (ctx->d_subtexel, which must be there)
-int launch_apply_rgba_fb_bilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
-                                  const uint8_t *d_lut);
-// ... with the four positions resolved one by one: those outside the plate through ctx->d_seam (which must be current)
-int launch_apply_rgba_fb_bilinear_seams(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst,
-                                        int dst_pitch, const uint8_t *d_lut);
+                         const uint8_t *d_lut, FbMode mode);
 int coopmap_stats(bk_ctx *ctx, int out[6]);   // blocks, direct-gather blocks, empty blocks, LDS bytes per buffer
 int coopmap_traffic_model(bk_ctx *ctx, uint64_t out[8]);
 int coopmap_xcd_probe(bk_ctx *ctx, int *out, int nwg);

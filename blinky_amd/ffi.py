@@ -210,6 +210,23 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _lut(lut):
+    """a truecolour apply's byte LUTs (None: none) -> the contiguous uint8 [4][6][256] array the caller keeps alive across the call"""
+    if lut is None:
+        return None
+    lut = np.ascontiguousarray(lut, dtype=np.uint8)
+    if lut.shape != (4, MAX_PLATES, 256):
+        raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+    return lut
+
+
+def _fb_plates(plates, pitches):
+    """six device addresses (int / c_void_p / None) and their six row pitches -> the two arrays the frame-buffer applies take"""
+    if len(plates) != MAX_PLATES or len(pitches) != MAX_PLATES:
+        raise ValueError(f"plates and pitches must have {MAX_PLATES} entries")
+    return ((_vp * MAX_PLATES)(*[p.value if isinstance(p, C.c_void_p) else p for p in plates]), (_i * MAX_PLATES)(*[int(p) for p in pitches]))
+
+
 class Context:
     """Thin object wrapper over a ``bk_ctx*``."""
 
@@ -517,20 +534,14 @@ class Context:
     def apply_rgba_tinted_device(self, dst_ptr, pitch, frame_stride, lut, globe0=0, nframes=1, x0=0, y0=0):
         """apply_rgba_device with rubix: byte c of a mapped pixel of tint t < 6 leaves as lut[c][t][v]; lut: uint8 [4][6][256]
         (create_tintmap_rgba makes the reference's tints)"""
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8)
-            if lut.shape != (4, MAX_PLATES, 256):
-                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        lut = _lut(lut)
         self._chk(lib.bk_apply_rgba_tinted_device(self._h, globe0, nframes, dst_ptr, pitch, frame_stride, x0, y0, _ptr(lut)))
 
     def apply_rgba_ss2_device(self, dst_ptr, pitch, frame_stride, globe0=0, nframes=1, x0=0, y0=0, lut=None):
         """2x2 supersampling: the context is W x H, the frames written are (W + 1) // 2 x (H + 1) // 2 truecolour pixels, each the
         rounded mean of its mapped samples; lut None: the samples of apply_rgba_device, else of apply_rgba_tinted_device through
         lut (uint8 [4][6][256]).  pitch / frame_stride in bytes and x0 / y0 in pixels of the half-size frames"""
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8)
-            if lut.shape != (4, MAX_PLATES, 256):
-                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        lut = _lut(lut)
         self._chk(lib.bk_apply_rgba_ss2_device(self._h, globe0, nframes, dst_ptr, pitch, frame_stride, x0, y0, _ptr(lut)))
 
     def apply_rgba_fb_device(self, plates, pitches, dst_ptr, dst_pitch, x0=0, y0=0, lut=None, ss2=False):
@@ -538,42 +549,24 @@ class Context:
         ring slot, no block map.  plates: six device addresses (int / c_void_p; None for a plate whose footprint is empty), pitches:
         their row pitches in bytes; lut None: plain, else uint8 [4][6][256]; ss2: the 2x2-supersampled half-size frame.  The frame is
         byte for byte what upload_plate_rgba_device + apply_rgba_device / _tinted_device / _ss2_device write"""
-        if len(plates) != MAX_PLATES or len(pitches) != MAX_PLATES:
-            raise ValueError(f"plates and pitches must have {MAX_PLATES} entries")
-        pp = (_vp * MAX_PLATES)(*[p.value if isinstance(p, C.c_void_p) else p for p in plates])
-        pi = (_i * MAX_PLATES)(*[int(p) for p in pitches])
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8)
-            if lut.shape != (4, MAX_PLATES, 256):
-                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        pp, pi = _fb_plates(plates, pitches)
+        lut = _lut(lut)
         self._chk(lib.bk_apply_rgba_fb_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut), int(ss2)))
 
     def apply_rgba_fb_bilinear_device(self, plates, pitches, dst_ptr, dst_pitch, x0=0, y0=0, lut=None):
         """apply_rgba_fb_device with bilinear texel filtering through the sub-texel plane (set_subtexel(True) before the build): every
         mapped pixel is the exact integer blend of the four texels of its own plate around its position; a tint is applied to each
         texel before the blend.  Reads texels within one texel of a named one, clamped to the plate"""
-        if len(plates) != MAX_PLATES or len(pitches) != MAX_PLATES:
-            raise ValueError(f"plates and pitches must have {MAX_PLATES} entries")
-        pp = (_vp * MAX_PLATES)(*[p.value if isinstance(p, C.c_void_p) else p for p in plates])
-        pi = (_i * MAX_PLATES)(*[int(p) for p in pitches])
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8)
-            if lut.shape != (4, MAX_PLATES, 256):
-                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        pp, pi = _fb_plates(plates, pitches)
+        lut = _lut(lut)
         self._chk(lib.bk_apply_rgba_fb_bilinear_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut)))
 
     def apply_rgba_fb_bilinear_seams_device(self, plates, pitches, dst_ptr, dst_pitch, x0=0, y0=0, lut=None):
         """apply_rgba_fb_bilinear_device that filters ACROSS plate seams: each of the four positions is resolved on its own, one outside
         the pixel's plate through the seam table (read_seam_table / set_seam_table); a NULL entry, or one into a plate passed as None,
         clamps as apply_rgba_fb_bilinear_device does.  All four texels go through the pixel's tint"""
-        if len(plates) != MAX_PLATES or len(pitches) != MAX_PLATES:
-            raise ValueError(f"plates and pitches must have {MAX_PLATES} entries")
-        pp = (_vp * MAX_PLATES)(*[p.value if isinstance(p, C.c_void_p) else p for p in plates])
-        pi = (_i * MAX_PLATES)(*[int(p) for p in pitches])
-        if lut is not None:
-            lut = np.ascontiguousarray(lut, dtype=np.uint8)
-            if lut.shape != (4, MAX_PLATES, 256):
-                raise ValueError(f"lut must be uint8 [4][{MAX_PLATES}][256], not {lut.shape}")
+        pp, pi = _fb_plates(plates, pitches)
+        lut = _lut(lut)
         self._chk(lib.bk_apply_rgba_fb_bilinear_seams_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut)))
 
     def read_seam_table(self):
