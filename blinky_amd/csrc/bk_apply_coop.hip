@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "bk_internal.h"
+#include "bk_resident_plan.h"
 
 namespace bk {
 

@@ -581,7 +581,6 @@ struct Resident {
     uint8_t *d_pal = nullptr;          // the session's OWN copy of the tint LUTs (ctx->pal.d belongs to whoever applied last)
     int *d_phase = nullptr;            // every workgroup's frame phase (frame stride, r5)
     int cap_phase = 0;                 // ints allocated behind d_phase
-    int form = 1;
     int stride = 1;                    // frame stride of the running session (r5)
     bool direct = false;               // commands are written into the device copies by the host itself (large BAR, r5)
     int ncopies = 1;                   // device copies of the command ring of the running session
@@ -718,208 +717,166 @@ static int res_variant_rg(bk_ctx *ctx, Resident *R, int rg, const ResArgs &a, si
                                                                                                 : res_variant<4, false>(ctx, R, a, shmem, K, nq, launch, places);
 }
 
-// Who does what.  The grid is `places` workgroups (all of them resident at once); the last one is the service workgroup, and the
-// seven that share its CU - the hardware deals an XCD's workgroups round the XCD's 32 CUs: grid positions service - 256 m - sleep,
-// when the grid is large enough for it to matter.  A worker with grid position b runs on XCD b % 8 (observed dispatch order,
-// MI355X_MICROARCH.md; only locality hangs on it) and takes blocks of "its" stretch of the live blocks in walk order, the stretches
-// cut so that their cost is proportional to the XCD's workers; inside a stretch the blocks are dealt in rounds of one block per
-// worker (a round is a compact piece of the screen: the lines neighbouring blocks share meet in the XCD's L2), within a round the
-// dearest block to the worker that has the least so far - the frame is as long as its slowest workgroup, and whole-globe lenses
-// have blocks of 300 and of 1500 chunks.  cost of a block = 256 + its chunks (measured: a workgroup's frame time goes with the chunks it stages) + 1200 if it overflows the register plan.
-struct ResPlan { int grid = 0, service = 0, depth = 1, workers = 0; std::vector<int> assign, phase; };
-static void res_plan(const std::vector<CoopHdr> &hdr, const std::vector<uint32_t> &order, int places, int depth_cap, int nq_chunks, ResPlan *P, int ncu = 256)
+// Who does what - which workgroup warps which blocks in which frame phase - and which of the forms above serves a block map is decided in
+// bk_resident_plan.cpp, from plain values: what follows reads the map back, asks there, and launches what it is told.
+struct ResMapHost { std::vector<uint32_t> nchunks, order, lines; };      // per block: chunks; the live blocks in walk order; per block: cost in lines
+
+static int res_read_map(bk_ctx *ctx, const CoopMap *cm, ResMapHost *m)
 {
-    const int nlive = (int)order.size();
-    int grid = places;
-    std::vector<char> role((size_t)grid, 0);                   // 0 worker, 1 sleeper, 2 service
-    auto set_roles = [&]() {
-        role.assign((size_t)grid, 0);
-        role[(size_t)grid - 1] = 2;
-        // (the workgroups b and b + ncu share a CU: an XCD's workgroups go round its CUs)
-        if (grid >= 4 * ncu) for (int m = 1; m <= 7 && grid - 1 - ncu * m >= 0; ++m) role[(size_t)(grid - 1 - ncu * m)] = 1;
-    };
-    set_roles();
-    auto count_workers = [&]() { int n = 0; for (char r : role) n += r == 0; return n; };
-    int workers = count_workers();
-    // one block each when the map allows it: no more workgroups than blocks (+ the service CU's)
-    if (workers > nlive && nlive > 0) {
-        while (grid > 9 && workers > nlive) { --grid; set_roles(); workers = count_workers(); }
-        while (workers < nlive) { ++grid; set_roles(); workers = count_workers(); }
-    }
-    std::vector<std::vector<int>> wx(8);                        // the workers of every XCD, by grid position
-    for (int b = 0; b < grid; ++b) if (role[(size_t)b] == 0) wx[(size_t)(b & 7)].push_back(b);
-    auto cost_of = [&](uint32_t blk) { return 256.0 + (double)hdr[blk].nchunks + (hdr[blk].nchunks > (uint32_t)nq_chunks ? 1200.0 : 0.0); };
-    // Which XCD takes which blocks.  The walk is cut into SEGMENTS of 24 consecutive live blocks (the walk goes down patches of 8
-    // block rows column by column: a segment is a compact 3 x 8 piece of the screen, most of a block's neighbours - the blocks it
-    // shares globe lines with - are in its own segment), and the segments are dealt to the XCDs dearest first, each to the XCD
-    // that has the least cost per worker so far and room left (a worker holds at most depth_cap blocks).  Contiguous eighths of
-    // the walk - one stretch per XCD, as the launch-per-frame kernel's bands - cannot be balanced by cost AND by count at once:
-    // 4K hammer in three blocks per worker left 2360 chunks per worker on the XCDs that own the cube's corners and 1306 on the
-    // ones in between, and the frame is as long as its slowest workgroup.
-    std::vector<std::vector<int>> xb(8);                        // per XCD: positions in `order`
-    {
-        const int SEG = 24;
-        struct Seg { int lo, hi; double cost; };
-        std::vector<Seg> segs;
-        for (int l = 0; l < nlive; l += SEG) {
-            Seg sg = {l, std::min(nlive, l + SEG), 0.0};
-            for (int i = sg.lo; i < sg.hi; ++i) sg.cost += cost_of(order[(size_t)i]);
-            segs.push_back(sg);
-        }
-        std::sort(segs.begin(), segs.end(), [](const Seg &p, const Seg &q) { return p.cost > q.cost || (p.cost == q.cost && p.lo < q.lo); });
-        std::vector<double> xcost(8, 0.0);
-        for (const Seg &sg : segs) {
-            int l = sg.lo;
-            while (l < sg.hi) {
-                int best = -1;
-                for (int x = 0; x < 8; ++x) {
-                    const int nw = (int)wx[(size_t)x].size();
-                    if (nw == 0) continue;
-                    const int room = depth_cap > 0 ? nw * depth_cap - (int)xb[(size_t)x].size() : nlive;
-                    if (room <= 0) continue;
-                    if (best < 0 || xcost[(size_t)x] / nw < xcost[(size_t)best] / (double)wx[(size_t)best].size()) best = x;
-                }
-                if (best < 0) break;                            // (does not fit under the cap: the caller tries the next form)
-                const int nw = (int)wx[(size_t)best].size();
-                const int room = depth_cap > 0 ? nw * depth_cap - (int)xb[(size_t)best].size() : nlive;
-                const int take = std::min(room, sg.hi - l);     // (a segment that does not fit whole is split)
-                for (int i = 0; i < take; ++i) { xb[(size_t)best].push_back(l + i); xcost[(size_t)best] += cost_of(order[(size_t)(l + i)]); }
-                l += take;
-            }
-            if (l < sg.hi) break;
-        }
-    }
-    int placed = 0, depth = 1;
-    for (int x = 0; x < 8; ++x) {
-        std::sort(xb[(size_t)x].begin(), xb[(size_t)x].end());
-        placed += (int)xb[(size_t)x].size();
-        const int nb = (int)xb[(size_t)x].size(), nw = (int)wx[(size_t)x].size();
-        if (nw > 0) depth = std::max(depth, (nb + nw - 1) / nw);
-    }
-    if (placed < nlive) depth = std::max(depth, depth_cap + 1);             // (does not fit under the cap)
-    P->grid = grid; P->service = grid - 1; P->depth = depth; P->workers = workers;
-    P->assign.assign((size_t)grid * depth, -1);
-    for (int b = 0; b < grid; ++b) if (role[(size_t)b] == 1) P->assign[(size_t)b * depth] = -2;
-    for (int x = 0; x < 8; ++x) {
-        const std::vector<int> &w = wx[(size_t)x];
-        const int nw = (int)w.size();
-        if (nw == 0) continue;
-        // the dearest block first, each to the worker that has the least so far and still a place free; a worker then takes its
-        // blocks in walk order, so that at any moment the workers of an XCD are still on neighbouring pieces of the screen
-        std::vector<double> have((size_t)nw, 0.0);
-        std::vector<std::vector<int>> mine((size_t)nw);
-        std::vector<int> bidx = xb[(size_t)x];
-        std::sort(bidx.begin(), bidx.end(), [&](int p, int q) { const double cp = cost_of(order[(size_t)p]), cq = cost_of(order[(size_t)q]); return cp > cq || (cp == cq && p < q); });
-        // (a heap of workers by load: 3000 blocks x 128 workers needs no better than a scan)
-        for (int l : bidx) {
-            int best = -1;
-            for (int i = 0; i < nw; ++i)
-                if ((int)mine[(size_t)i].size() < depth && (best < 0 || have[(size_t)i] < have[(size_t)best])) best = i;
-            if (best < 0) break;
-            mine[(size_t)best].push_back(l);
-            have[(size_t)best] += cost_of(order[(size_t)l]);
-        }
-        for (int i = 0; i < nw; ++i) {
-            std::sort(mine[(size_t)i].begin(), mine[(size_t)i].end());
-            for (size_t k = 0; k < mine[(size_t)i].size(); ++k) P->assign[(size_t)w[(size_t)i] * depth + k] = (int)order[(size_t)mine[(size_t)i][k]];
-        }
-    }
+    const int nblocks = cm->blocks_x * cm->blocks_y;
+    uint32_t bands[9];
+    std::vector<CoopHdr> hdr((size_t)nblocks);
+    BK_HIP(ctx, hipMemcpyAsync(bands, cm->d_bands, sizeof bands, hipMemcpyDeviceToHost, ctx->stream));
+    BK_HIP(ctx, hipMemcpyAsync(hdr.data(), cm->d_hdr, hdr.size() * sizeof(CoopHdr), hipMemcpyDeviceToHost, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (block map, palette upload, whatever filled the globes: done before the kernel starts)
+    m->order.resize((size_t)bands[8]);
+    if (bands[8]) BK_HIP(ctx, hipMemcpy(m->order.data(), cm->d_order, m->order.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    m->lines.resize((size_t)nblocks);                    // what the block map's compile counted per block: 128-byte lines staged + a share per pixel + a constant
+    BK_HIP(ctx, hipMemcpy(m->lines.data(), cm->d_cost, m->lines.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    m->nchunks.resize((size_t)nblocks);
+    for (int i = 0; i < nblocks; ++i) m->nchunks[(size_t)i] = hdr[(size_t)i].nchunks;
+    return BK_OK;
 }
 
-// Who does what when the map is dealt out to several STRIDE GROUPS (r5).  A workgroup's frame time goes with the NUMBER of its blocks first
-// and with their bytes second (profiles/r05_resident_apply.txt), so every worker of a group gets the same number of blocks (+- 1) and,
-// within that, the same cost.  XCD x (grid position % 8) takes a contiguous stretch of the walk - neighbouring
-// blocks share globe lines, and an XCD's L2 is where they meet - whose length is proportional to its workers; inside the stretch
-// the dearest block goes to the worker with the least cost among those with the fewest blocks.
-static void res_plan_stride(const std::vector<CoopHdr> &hdr, const std::vector<uint32_t> &order, int places, int stride_groups, ResPlan *P)
+// form, grid, stride and plan for the map (res_choose); how many workgroups of a form the device holds is the occupancy API's to say
+static int res_choose_form(bk_ctx *ctx, Resident *R, const CoopMap *cm, const ResMapHost &m, size_t staging, bool may_grow, ResChoice *c)
 {
-    const int nlive = (int)order.size();
-    int grid = places;
-    std::vector<char> role;
-    auto set_roles = [&]() {
-        role.assign((size_t)grid, 0);
-        role[(size_t)grid - 1] = 2;
-        if (grid >= 1024 && stride_groups == 1) for (int m = 1; m <= 7 && grid - 1 - 256 * m >= 0; ++m) role[(size_t)(grid - 1 - 256 * m)] = 1;
-    };
-    set_roles();
-    auto count_workers = [&]() { int n = 0; for (char r : role) n += r == 0; return n; };
-    int workers = count_workers();
-    // no more workers than block copies - plus a few: the groups take an XCD's workers in turn, so their sizes differ by up to one
-    // worker per XCD, and every group needs a worker per block
-    const int want = nlive * stride_groups + (stride_groups > 1 ? 8 * stride_groups : 0);
-    if (workers > want && nlive > 0) {
-        while (grid > 9 && workers > want) { --grid; set_roles(); workers = count_workers(); }
-        while (workers < want && grid < places) { ++grid; set_roles(); workers = count_workers(); }
-    }
-    // stride groups: worker number w (in grid order) belongs to group w % stride_groups - every group is spread over all XCDs
-    std::vector<int> wpos;
-    for (int b = 0; b < grid; ++b) if (role[(size_t)b] == 0) wpos.push_back(b);
-    P->grid = grid; P->service = grid - 1; P->workers = workers;
-    P->phase.assign((size_t)grid, 0);
-    int depth = 1;
-    std::vector<std::vector<int>> mine((size_t)workers);
-    for (int g = 0; g < stride_groups; ++g) {
-        std::vector<int> gw;                                      // this group's workers (indices into wpos)
-        // (every XCD's workers go to the groups in turn, so that every group - every frame - is spread over all eight XCDs; "worker w to
-        //  group w % stride" would put a whole group on ONE XCD when the stride is 8: consecutive grid positions are the eight XCDs)
-        {
-            int seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int w = 0; w < workers; ++w) { const int x = wpos[(size_t)w] & 7; if (seen[x]++ % stride_groups == g) gw.push_back(w); }
-        }
-        const int ngw = (int)gw.size();
-        if (ngw == 0) continue;
-        std::vector<std::vector<int>> wx(8);
-        for (int i : gw) wx[(size_t)(wpos[(size_t)i] & 7)].push_back(i);
-        // stretches of the walk by worker count (largest remainder keeps the per-worker counts within one of each other)
-        int lo = 0, wseen = 0;
-        for (int x = 0; x < 8; ++x) {
-            const int nw = (int)wx[(size_t)x].size();
-            wseen += nw;
-            const int hi = (int)((long long)nlive * wseen / ngw);
-            if (nw > 0) {
-                std::vector<int> idx;
-                for (int l = lo; l < hi; ++l) idx.push_back(l);
-                std::sort(idx.begin(), idx.end(), [&](int p, int q) { const uint32_t cp = hdr[order[(size_t)p]].nchunks, cq = hdr[order[(size_t)q]].nchunks; return cp > cq || (cp == cq && p < q); });
-                std::vector<double> have((size_t)nw, 0.0);
-                std::vector<int> cntw((size_t)nw, 0);
-                for (int l : idx) {
-                    int best = 0;
-                    for (int i = 1; i < nw; ++i)
-                        if (cntw[(size_t)i] < cntw[(size_t)best] || (cntw[(size_t)i] == cntw[(size_t)best] && have[(size_t)i] < have[(size_t)best])) best = i;
-                    mine[(size_t)wx[(size_t)x][(size_t)best]].push_back(l);
-                    have[(size_t)best] += 256.0 + hdr[order[(size_t)l]].nchunks;
-                    ++cntw[(size_t)best];
-                }
-            }
-            lo = hi;
-        }
-        for (int i : gw) P->phase[(size_t)wpos[(size_t)i]] = g;
-    }
-    for (auto &m : mine) depth = std::max(depth, (int)m.size());
-    P->depth = depth;
-    P->assign.assign((size_t)grid * depth, -1);
-    for (int b = 0; b < grid; ++b) if (role[(size_t)b] == 1) P->assign[(size_t)b * depth] = -2;
-    for (int w = 0; w < workers; ++w) {
-        std::sort(mine[(size_t)w].begin(), mine[(size_t)w].end());            // a worker takes its blocks in walk order
-        for (size_t k = 0; k < mine[(size_t)w].size(); ++k) P->assign[(size_t)wpos[(size_t)w] * depth + k] = (int)order[(size_t)mine[(size_t)w][k]];
-    }
-}
-
-// (re)launch the kernel for the context's current block map
-// force_rg != 0: over blocks of that height (ensure_coopmap's force_rg) - a session growing its blocks, res_relaunch_taller
-static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0, int force_rg = 0);
-
-// the session's block map does not serve it at this block height: compile it twice as tall and launch over that; the map remembers
-// (`grown_rg`) that this height is a session's doing
-static int res_relaunch_taller(bk_ctx *ctx, Resident *R, CoopMap *cm, int shape_tries)
-{
-    cm->valid = false;
-    const int rc = res_launch(ctx, R, shape_tries + 1, cm->rg * 2);
-    if (ctx->coopmap && ctx->coopmap->valid) ctx->coopmap->grown_rg = ctx->coopmap->rg;
+    ResChoiceIn in;
+    in.max_chunks = cm->stats[CS_MAX_CHUNKS]; in.rg = cm->rg; in.tinted = R->rubix;
+    in.no_one_block = (ctx->apply_flags & BK_RF_NO_ONE_BLOCK) != 0; in.no_tables = (ctx->apply_flags & BK_RF_NO_TABLES) != 0; in.no_stride = (ctx->apply_flags & BK_RF_NO_STRIDE) != 0;
+    in.may_grow = may_grow; in.ncu = ctx->res_parts > 1 ? RES_NO_SLEEPERS : ctx->num_cus; in.staging_bytes = staging;
+    int rc = BK_OK;                                      // (of the first question that failed: nothing is asked after it)
+    *c = res_choose(m.nchunks, m.order, in, [&](int form, size_t shmem) {
+        int places = 0;
+        if (rc == BK_OK) rc = res_variant_rg(ctx, R, cm->rg, ResArgs{}, shmem, form, res_nq(in.max_chunks), false, &places);
+        return rc == BK_OK ? places : 0;
+    });
     return rc;
 }
 
-static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries, int force_rg)
+// the two developer prints (g_debug.print_model): the plan before the launch, the laggards after the session
+static void res_print_plan(const ResMapHost &m, const ResChoice &c, uint32_t max_chunks, int lds_buf)
+{
+    const ResPlan &plan = c.plan;
+    int big = 0, big4 = 0;
+    for (uint32_t b : m.order) { big += m.nchunks[b] > 1536u; big4 += m.nchunks[b] > 1024u; }
+    double mx = 0, sum = 0; int nw = 0;                    // cost per workgroup: 1024 a block + its chunks
+    for (int x = 0; x < 8; ++x) {
+        double xs = 0, xm = 0; int xn = 0, xb = 0;
+        for (int b = x; b < plan.grid; b += 8) {
+            double cost = 0; int nbk = 0;
+            for (int k = 0; k < plan.depth; ++k) { const int v = plan.assign[(size_t)b * plan.depth + k]; if (v >= 0) { cost += m.nchunks[(size_t)v]; ++nbk; } }
+            if (nbk) { ++xn; xb += nbk; xs += cost; xm = std::max(xm, cost); ++nw; sum += cost + 1024.0 * nbk; mx = std::max(mx, cost + 1024.0 * nbk); }
+        }
+        fprintf(stderr, "RESIDENT plan XCD %d: %d workers, %d blocks, chunks per worker mean %.0f max %.0f\n", x, xn, xb, xn ? xs / xn : 0.0, xm);
+    }
+    fprintf(stderr, "RESIDENT plan: %u live blocks (max %u chunks, %d above 1024, %d above 1536), grid %d depth %d K %d nq %d lds %d, cost per workgroup mean %.0f max %.0f\n",
+            (unsigned)m.order.size(), max_chunks, big4, big, plan.grid, plan.depth, c.form, res_nq(max_chunks), lds_buf, nw ? sum / nw : 0.0, mx);
+}
+// raw: every workgroup's word of d_up (workers leave 0x80000000 | figure behind); figures: the workers' figures, ascending
+static void res_print_laggards(const Resident *R, const std::vector<uint32_t> &raw, const std::vector<uint32_t> &figures)
+{
+    if (FILE *df = fopen("gpurun_out/res_wg_stats.txt", "w")) {          // (developer: every workgroup's figure + its blocks' chunks / lines)
+        for (size_t i = 0; i < raw.size(); ++i) {
+            if (!(raw[i] & 0x80000000u)) continue;
+            fprintf(df, "%zu %u", i, raw[i] & 0x7FFFFFFFu);
+            for (int k = 0; k < R->depth; ++k) { const int v = R->plan_assign[i * R->depth + k]; if (v >= 0) fprintf(df, " %d:%u:%u", v, R->plan_hdr_chunks[(size_t)v], R->plan_lines[(size_t)v]); }
+            fprintf(df, "\n");
+        }
+        fclose(df);
+    }
+    fprintf(stderr, "RESIDENT laggards (workgroup:streamed frames[chunks of its blocks]):");
+    int shown = 0;
+    const uint32_t cut = figures.size() > 16 ? figures[figures.size() - 16] : 0;
+    for (size_t i = 0; i < raw.size() && shown < 24; ++i)
+        if ((raw[i] & 0x80000000u) && (raw[i] & 0x7FFFFFFFu) >= cut) {
+            fprintf(stderr, " %zu:%u[", i, raw[i] & 0x7FFFFFFFu);
+            for (int k = 0; k < R->depth; ++k) { const int v = R->plan_assign[i * R->depth + k]; if (v >= 0) fprintf(stderr, "%u/%u ", R->plan_hdr_chunks[(size_t)v], R->plan_lines[(size_t)v]); }
+            fprintf(stderr, "]");
+            ++shown;
+        }
+    fprintf(stderr, "\n");
+}
+
+// at least `need` elements behind *p, of *cap allocated: if not, `alloc` new ones (what the old ones held was the last launch's)
+template <typename T, typename N>
+static int res_grow(bk_ctx *ctx, T **p, N *cap, size_t need, size_t alloc)
+{
+    if (*p && (size_t)*cap >= need) return BK_OK;
+    (void)hipFree(*p); *p = nullptr; *cap = 0;
+    BK_HIP(ctx, hipMalloc((void **)p, alloc * sizeof(T)));
+    *cap = (N)alloc;
+    return BK_OK;
+}
+
+static int res_grow_buffers(bk_ctx *ctx, Resident *R, const ResPlan &plan)
+{
+    const size_t nflags = (size_t)((plan.grid + 2048) / 2048 * 2048);      // (the collector reads the flags 2048 at a time)
+    int cap_up = R->cap_wg, r = res_grow(ctx, &R->d_done, &R->cap_wg, (size_t)plan.grid, nflags);
+    if (!r) r = res_grow(ctx, &R->d_up, &cap_up, (size_t)plan.grid, nflags);
+    if (r) { R->cap_wg = 0; return r; }                  // (d_done and d_up: cap_wg words each, or to be allocated again)
+    if ((r = res_grow(ctx, &R->d_assign, &R->cap_assign, plan.assign.size(), plan.assign.size()))) return r;
+    return res_grow(ctx, &R->d_phase, &R->cap_phase, plan.phase.size(), std::max(plan.phase.size(), (size_t)R->cap_wg));
+}
+
+// the plan, the workgroups' flag words and an empty command ring, on the device before the kernel starts
+static int res_upload_plan(bk_ctx *ctx, Resident *R, const ResPlan &plan)
+{
+    memset((void *)R->h, 0, sizeof(ResHost));
+    // the flags: "done with everything" for the padding, the service workgroup and the sleepers; 0 for the workers
+    std::vector<uint32_t> flags((size_t)R->cap_wg, 0xFFFFFFFFu);
+    for (int b = 0; b < plan.grid; ++b) if (b != plan.service && plan.assign[(size_t)b * plan.depth] >= 0) flags[(size_t)b] = (uint32_t)plan.phase[(size_t)b];      // ("every frame of mine up to here": none yet)
+    // (a worker the plan gave no block - possible with a frame stride, per-XCD rounding - would otherwise have to walk the tickets for nothing: it is "done with everything" and leaves)
+    BK_HIP(ctx, hipMemcpyAsync(R->d_phase, plan.phase.data(), plan.phase.size() * sizeof(int), hipMemcpyHostToDevice, R->stream));
+    BK_HIP(ctx, hipMemcpyAsync(R->d_done, flags.data(), flags.size() * sizeof(uint32_t), hipMemcpyHostToDevice, R->stream));
+    BK_HIP(ctx, hipMemcpyAsync(R->d_assign, plan.assign.data(), plan.assign.size() * sizeof(int), hipMemcpyHostToDevice, R->stream));
+    BK_HIP(ctx, hipMemsetAsync(R->d_ring, 0, ((size_t)BK_RES_MAX_COPIES * BK_RES_COPY_WORDS + 64) * sizeof(uint32_t), R->stream));
+    BK_HIP(ctx, hipMemsetAsync(R->d_up, 0, (size_t)R->cap_wg * sizeof(uint32_t), R->stream));
+    BK_HIP(ctx, hipStreamSynchronize(R->stream));                     // (the host vector above goes away)
+    return BK_OK;
+}
+
+static ResArgs res_args(bk_ctx *ctx, const Resident *R, const CoopMap *cm, const ResChoice &c, int lds_buf)
+{
+    ResArgs a;
+    a.hdr = cm->d_hdr; a.list = cm->d_list; a.idx = cm->d_idx; a.tint_t = ctx->d_tints; a.lmap = ctx->d_offsets;
+    a.globe = ctx->d_globe; a.globe_stride = ctx->globe_stride(); a.globe_frames = ctx->nframes;
+    a.W = ctx->W; a.rows = ctx->rows(); a.blocks_x = cm->blocks_x; a.nblocks = cm->blocks_x * cm->blocks_y; a.lds_buf = lds_buf;
+    a.pal = R->d_pal; a.kflags = (ctx->apply_flags & BK_RF_KERNEL_MASK) | (R->direct ? BK_KF_DIRECT : 0);       // (the mask: see BkResidentFlag)
+    a.rh = R->h; a.idle_ticks = (uint32_t)std::min(4.0e9, R->idle_ms * 1e5);
+    a.ring = R->d_ring; a.wg_done = R->d_done; a.wg_up = R->d_up; a.nwg = c.plan.grid;
+    a.exit_flag = R->d_ring + (size_t)BK_RES_MAX_COPIES * BK_RES_COPY_WORDS;
+    a.assign = R->d_assign; a.depth = c.plan.depth; a.service = c.plan.service;
+    a.ncopies = std::max(1, std::min(BK_RES_MAX_COPIES, (c.plan.grid + 15) / 16));
+    // (direct submission: the HOST writes every copy, 32 bytes each through the BAR - 128 copies cost 4.4 us per submit; one to eight
+    //  poll equally well (measured), four cost ~0.2 us)
+    if (R->direct) a.ncopies = std::min(a.ncopies, 4);
+    a.stride = c.stride; a.phase = R->d_phase;
+    return a;
+}
+
+// every workgroup has to be ON the device: one that waits for a place would only start when the others leave.  The occupancy
+// the API reports can be one more than the hardware admits (SGPR granules: MI355X_MICROARCH.md, "Residency"), so look.
+// *resident = false: the kernel was sent away again, the next launch is to leave one place more per CU free
+static int res_await_residency(bk_ctx *ctx, Resident *R, bool *resident)
+{
+    *resident = true;
+    const uint64_t t0 = res_now_ns();
+    while (R->h->up < (uint32_t)R->nwg - 1u && !R->h->exited) {
+        if (res_now_ns() - t0 <= 50000000ull) continue;               // 50 ms
+        const uint32_t up = R->h->up;
+        if (int r = res_drain(ctx, R, true)) return r;
+        if (R->shrink >= 6) return ctx->fail(BK_E_HIP, "resident apply: only %u of %d workgroups became resident", up, R->nwg);
+        ++R->shrink;
+        *resident = false;
+        break;
+    }
+    return BK_OK;
+}
+
+// (re)launch the kernel for the context's current block map
+// force_rg != 0: over blocks of that height (ensure_coopmap's force_rg) - a session growing its blocks
+static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries = 0, int force_rg = 0)
 {
     // a session outlives resident_quiesce: after a bk_resize / bk_set_rows / failed bk_build in between there may be no lensmap (or
     // no rows) to compile a block map from - say so instead of launching on freed tables (bk_apply_device's answer to the same state)
@@ -928,189 +885,40 @@ static int res_launch(bk_ctx *ctx, Resident *R, int shape_tries, int force_rg)
     if (int r = ensure_coopmap(ctx, 1, R->rubix ? 1 : 0, force_rg)) return r;
     CoopMap *cm = ctx->coopmap;
     if (int r = coop_stats_wait(ctx, cm)) return r;
-    const int nblocks = cm->blocks_x * cm->blocks_y;
-    uint32_t bands[9];
-    std::vector<CoopHdr> hdr((size_t)nblocks);
-    BK_HIP(ctx, hipMemcpyAsync(bands, cm->d_bands, sizeof bands, hipMemcpyDeviceToHost, ctx->stream));
-    BK_HIP(ctx, hipMemcpyAsync(hdr.data(), cm->d_hdr, hdr.size() * sizeof(CoopHdr), hipMemcpyDeviceToHost, ctx->stream));
-    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (block map, palette upload, whatever filled the globes: done before the kernel starts)
-    const uint32_t nlive = bands[8];
-    std::vector<uint32_t> order((size_t)nlive);
-    if (nlive) BK_HIP(ctx, hipMemcpy(order.data(), cm->d_order, order.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> lines((size_t)nblocks);            // what the block map's compile counted per block: 128-byte lines staged + a share per pixel + a constant
-    BK_HIP(ctx, hipMemcpy(lines.data(), cm->d_cost, lines.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const int rg = cm->rg;
-    R->form = 1;
+    ResMapHost m;
+    if (int r = res_read_map(ctx, cm, &m)) return r;
     // the staging buffer holds the largest listed block of the map (the launch-per-frame kernel may run with a smaller one and
     // take such blocks in passes; here they would fall to the direct gather)
     int lds_buf = (int)std::min<uint32_t>(cm->stats[CS_MAX_CHUNKS], BK_COOP_MAX_CHUNKS + 1) * 16;
     lds_buf = std::max(1024, (lds_buf + 1023) & ~1023);
-    const size_t shmem = (size_t)lds_buf + (R->rubix ? BK_PAL_BYTES : 0);
-    ResArgs a;
-    a.hdr = cm->d_hdr; a.list = cm->d_list; a.idx = cm->d_idx; a.tint_t = ctx->d_tints; a.lmap = ctx->d_offsets;
-    a.globe = ctx->d_globe; a.globe_stride = ctx->globe_stride(); a.globe_frames = ctx->nframes;
-    a.W = ctx->W; a.rows = ctx->rows(); a.blocks_x = cm->blocks_x; a.nblocks = nblocks; a.lds_buf = lds_buf;
-    a.pal = R->d_pal; a.kflags = ctx->apply_flags & BK_RF_KERNEL_MASK;       // (+ BK_KF_DIRECT below; the mask: see BkResidentFlag)
-    a.rh = R->h; a.idle_ticks = (uint32_t)std::min(4.0e9, R->idle_ms * 1e5);
-    const int nq = cm->stats[CS_MAX_CHUNKS] > 1024u ? 6 : 4;
-    // The smallest form whose grid holds every block of the map on the chip: one, two or three blocks per workgroup with their chunk
-    // offsets in registers; if the map needs more, blocks twice as tall first (a workgroup's frame time goes with the NUMBER of its
-    // blocks - one trip to memory each, measured 2.5 us - so the same screen in taller blocks is less work: 4K mercator at 128 x 16 is
-    // 4050 live blocks, at 128 x 32 half that); then (r5) four, six or eight blocks per workgroup with the offsets in an LDS table;
-    // and only a map that exceeds that too (8K: its chunk offsets alone are the size of the chip's LDS) keeps eight (or three) blocks
-    // per workgroup resident and fetches the rest of its block map per frame, as a launch would.
-    int K = 1, places = 0;
-    ResPlan plan;
-    const uint32_t tab_row = std::min<uint32_t>((cm->stats[CS_MAX_CHUNKS] + 255u) & ~255u, (uint32_t)nq * 256u) * 4u;      // bytes of table per block, worst case
-    auto form_shmem = [&](int form) -> size_t { return shmem + (form == 4 || form == 6 || form == 8 ? (size_t)form * tab_row : form == 10 ? 8 * (size_t)tab_row : 0); };
-    auto try_form = [&](int form, int depth_cap, bool *ok) -> int {
-        *ok = false;
-        if (form_shmem(form) > 160 * 1024 - 512) return BK_OK;
-        if (int r = res_variant_rg(ctx, R, rg, a, form_shmem(form), form, nq, false, &places)) return r;
-        if (places < 9) return BK_OK;
-        res_plan(hdr, order, places, depth_cap, (form == 1 ? 4 : nq) * 256, &plan, ctx->res_parts > 1 ? 1 << 30 : ctx->num_cus);
-        *ok = depth_cap == 0 || plan.depth <= depth_cap;
-        return BK_OK;
-    };
-    bool ok = false;
-    // (r6: ... and not from a map that a session's growth produced already - `grown_rg`: the next session of the same lensmap used to find
-    //  session 1's 128 x 16 map, grow it once more and take a form session 1 had not even looked at: 4K gumby 14.9 us per frame in the first
-    //  session, 35.5 in every later one, 256 workgroups of eight 128 x 32 blocks each)
-    const bool may_grow = rg < 4 && shape_tries < 2 && !coop_forced_rg(ctx, force_rg) && cm->grown_rg != rg;
-    {
-        for (int form : {1, 2, 3}) {
-            if (form == 1 && (nq > 4 || (ctx->apply_flags & BK_RF_NO_ONE_BLOCK))) continue;
-            K = form;
-            if (int r = try_form(form, form, &ok)) return r;
-            if (ok) break;
-        }
-        if (!ok && may_grow) return res_relaunch_taller(ctx, R, cm, shape_tries);
-        if (!ok && !(ctx->apply_flags & BK_RF_NO_TABLES) && !R->rubix)
-            for (int form : {4, 6, 8}) {
-                K = form;
-                if (int r = try_form(form, form, &ok)) return r;
-                if (ok) break;
-            }
-        if (!ok) {
-            // does not fit the chip: the rest is fetched per frame - with eight blocks resident (table) or with three (registers), whichever
-            // leaves less of the map to fetch
-            ResPlan p10; int places10 = 0; bool ok10 = false;
-            K = 10;
-            if (!(ctx->apply_flags & BK_RF_NO_TABLES) && !R->rubix) { if (int r = try_form(10, 0, &ok10)) return r; }
-            p10 = plan; places10 = places;
-            bool ok9 = false;
-            K = 9;
-            if (int r = try_form(9, 0, &ok9)) return r;
-            const double resident9 = ok9 ? std::min(1.0, 3.0 / std::max(1, plan.depth)) : -1.0, resident10 = ok10 ? std::min(1.0, 8.0 / std::max(1, p10.depth)) : -1.0;
-            if (resident10 > resident9 + 0.15) { K = 10; plan = p10; places = places10; ok = true; } else ok = ok9;
-        }
+    const size_t staging = (size_t)lds_buf + (R->rubix ? BK_PAL_BYTES : 0);
+    ResChoice c;
+    if (int r = res_choose_form(ctx, R, cm, m, staging, shape_tries < 2 && !coop_forced_rg(ctx, force_rg) && cm->grown_rg != cm->rg, &c)) return r;
+    if (c.verdict == ResChoice::NO_ROOM) return ctx->fail(BK_E_STATE, "resident apply: no room on the device for its workgroups (LDS %zu bytes each)", staging);
+    if (c.verdict == ResChoice::GROW) {
+        // the session's block map does not serve it at this block height: compile it twice as tall and launch over that; the map
+        // remembers (`grown_rg`) that this height is a session's doing
+        cm->valid = false;
+        const int rc = res_launch(ctx, R, shape_tries + 1, cm->rg * 2);
+        if (ctx->coopmap && ctx->coopmap->valid) ctx->coopmap->grown_rg = ctx->coopmap->rg;
+        return rc;
     }
-    if (!ok) return ctx->fail(BK_E_STATE, "resident apply: no room on the device for its workgroups (LDS %zu bytes each)", shmem);
-    // (r5) FRAME STRIDE: the plan uses a fraction of the places the form has (a 270-row stripe of a 4K frame is 255 blocks of 128 x 32 on
-    // 2048 places; 1080p is 510) - deal the map out `stride` times over, group p taking the frames p + 1, p + 1 + stride, ...  One frame
-    // at a time is not faster for it (a frame is still one trip per block), pipelined submissions are: `stride` frames side by side.
-    int stride = 1;
-    plan.phase.assign((size_t)plan.grid, 0);
-    if (K >= 1 && K <= 8 && !(ctx->apply_flags & BK_RF_NO_STRIDE) && plan.grid > 9) {
-        const int per_group = ((int)order.size() + K - 1) / K;              // workers one copy of the map needs at K blocks each
-        const int room = (places - 1) / std::max(1, per_group);
-        for (int st = std::min(8, room); st >= 2; --st) {
-            ResPlan p2;
-            res_plan_stride(hdr, order, places, st, &p2);
-            if (p2.depth <= K) { plan = p2; stride = st; break; }
-        }
-    }
-    // ... and a map of one block per workgroup that just fits (1080p hammer at 128 x 8: 1530 blocks on 2048 places) has no room for a
-    // second copy: blocks twice as tall are half as many, a trip to memory is hardly longer for them, and the stride doubles - 3.6 us per
-    // pipelined frame at 128 x 8, 1.35 at 128 x 32 with five frames side by side (stereographic, measured)
-    if (stride == 1 && K == 1 && may_grow && (int)order.size() * 2 > places && (int)order.size() > 64)
-        return res_relaunch_taller(ctx, R, cm, shape_tries);
-    const int grid = plan.grid;
-    R->plan_assign = plan.assign;
-    R->plan_hdr_chunks.resize(hdr.size());
-    for (size_t i = 0; i < hdr.size(); ++i) R->plan_hdr_chunks[i] = hdr[i].nchunks;
-    R->plan_lines = lines;
-    if (g_debug.print_model) {
-        int big = 0, big4 = 0;
-        for (uint32_t b : order) { big += hdr[b].nchunks > 1536u; big4 += hdr[b].nchunks > 1024u; }
-        double mx = 0, sum = 0; int nw = 0;
-        for (int b = 0; b < grid; ++b) {
-            double c = 0; bool w = false;
-            for (int k = 0; k < plan.depth; ++k) { const int v = plan.assign[(size_t)b * plan.depth + k]; if (v >= 0) { c += 1024.0 + hdr[(size_t)v].nchunks; w = true; } }
-            if (w) { ++nw; sum += c; mx = std::max(mx, c); }
-        }
-        for (int x = 0; x < 8; ++x) {
-            double xs = 0, xm = 0; int xn = 0, xb = 0;
-            for (int b = x; b < grid; b += 8) {
-                double c = 0; int nbk = 0;
-                for (int k = 0; k < plan.depth; ++k) { const int v = plan.assign[(size_t)b * plan.depth + k]; if (v >= 0) { c += hdr[(size_t)v].nchunks; ++nbk; } }
-                if (nbk) { ++xn; xb += nbk; xs += c; xm = std::max(xm, c); }
-            }
-            fprintf(stderr, "RESIDENT plan XCD %d: %d workers, %d blocks, chunks per worker mean %.0f max %.0f\n", x, xn, xb, xn ? xs / xn : 0.0, xm);
-        }
-        fprintf(stderr, "RESIDENT plan: %u live blocks (max %u chunks, %d above 1024, %d above 1536), grid %d depth %d K %d nq %d lds %d, cost per workgroup mean %.0f max %.0f\n",
-                nlive, cm->stats[CS_MAX_CHUNKS], big4, big, grid, plan.depth, K, nq, lds_buf, nw ? sum / nw : 0.0, mx);
-    }
-    if (grid > R->cap_wg) {
-        (void)hipFree(R->d_done); (void)hipFree(R->d_up);
-        R->d_done = R->d_up = nullptr; R->cap_wg = 0;
-        const int cap = (grid + 2048) / 2048 * 2048;                  // (the collector reads the flags 2048 at a time)
-        BK_HIP(ctx, hipMalloc((void **)&R->d_done, (size_t)cap * sizeof(uint32_t)));
-        BK_HIP(ctx, hipMalloc((void **)&R->d_up, (size_t)cap * sizeof(uint32_t)));
-        R->cap_wg = cap;
-    }
-    if (plan.assign.size() > R->cap_assign) {
-        (void)hipFree(R->d_assign); R->d_assign = nullptr; R->cap_assign = 0;
-        BK_HIP(ctx, hipMalloc((void **)&R->d_assign, plan.assign.size() * sizeof(int)));
-        R->cap_assign = plan.assign.size();
-    }
-    memset((void *)R->h, 0, sizeof(ResHost));
-    // the flags: "done with everything" for the padding, the service workgroup and the sleepers; 0 for the workers
-    std::vector<uint32_t> flags((size_t)R->cap_wg, 0xFFFFFFFFu);
-    for (int b = 0; b < grid; ++b) if (b != plan.service && plan.assign[(size_t)b * plan.depth] >= 0) flags[(size_t)b] = (uint32_t)plan.phase[(size_t)b];      // ("every frame of mine up to here": none yet)
-    // (a worker the plan gave no block - possible with a frame stride, per-XCD rounding - would otherwise have to walk the tickets for nothing: it is "done with everything" and leaves)
-    if (!R->d_phase || (int)plan.phase.size() > R->cap_phase) {        // (its own capacity: cap_wg has already been raised for this grid above)
-        (void)hipFree(R->d_phase); R->d_phase = nullptr;
-        R->cap_phase = std::max((int)plan.phase.size(), R->cap_wg);
-        BK_HIP(ctx, hipMalloc((void **)&R->d_phase, (size_t)R->cap_phase * sizeof(int)));
-    }
-    BK_HIP(ctx, hipMemcpyAsync(R->d_phase, plan.phase.data(), plan.phase.size() * sizeof(int), hipMemcpyHostToDevice, R->stream));
-    BK_HIP(ctx, hipMemcpyAsync(R->d_done, flags.data(), flags.size() * sizeof(uint32_t), hipMemcpyHostToDevice, R->stream));
-    BK_HIP(ctx, hipMemcpyAsync(R->d_assign, plan.assign.data(), plan.assign.size() * sizeof(int), hipMemcpyHostToDevice, R->stream));
-    BK_HIP(ctx, hipMemsetAsync(R->d_ring, 0, ((size_t)BK_RES_MAX_COPIES * BK_RES_COPY_WORDS + 64) * sizeof(uint32_t), R->stream));
-    BK_HIP(ctx, hipMemsetAsync(R->d_up, 0, (size_t)R->cap_wg * sizeof(uint32_t), R->stream));
-    BK_HIP(ctx, hipStreamSynchronize(R->stream));                     // (the host vectors above go away)
-    a.ring = R->d_ring; a.wg_done = R->d_done; a.wg_up = R->d_up; a.nwg = grid;
-    a.exit_flag = R->d_ring + (size_t)BK_RES_MAX_COPIES * BK_RES_COPY_WORDS;
-    a.assign = R->d_assign; a.depth = plan.depth; a.service = plan.service;
-    a.ncopies = std::max(1, std::min(BK_RES_MAX_COPIES, (grid + 15) / 16));
-    // (direct submission: the HOST writes every copy, 32 bytes each through the BAR - 128 copies cost 4.4 us per submit; one to eight
-    //  poll equally well (measured), four cost ~0.2 us)
-    if (R->direct) a.ncopies = std::min(a.ncopies, 4);
-    R->ncopies = a.ncopies;
-    if (R->direct) a.kflags |= BK_KF_DIRECT;
-    a.stride = stride; a.phase = R->d_phase; R->stride = stride;
-    R->nwg = grid; R->K = K == 9 ? 3 : K == 10 ? 8 : K; R->NQ = nq; R->rg = rg; R->per_cu = places / ctx->num_cus; R->depth = plan.depth; R->form = 1;
+    if (g_debug.print_model) res_print_plan(m, c, cm->stats[CS_MAX_CHUNKS], lds_buf);
+    if (int r = res_grow_buffers(ctx, R, c.plan)) return r;
+    if (int r = res_upload_plan(ctx, R, c.plan)) return r;
+    const ResArgs a = res_args(ctx, R, cm, c, lds_buf);
+    R->plan_assign = c.plan.assign; R->plan_hdr_chunks = std::move(m.nchunks); R->plan_lines = std::move(m.lines);
+    R->ncopies = a.ncopies; R->stride = c.stride; R->depth = c.plan.depth;
+    R->nwg = c.plan.grid; R->K = c.form == 9 ? 3 : c.form == 10 ? 8 : c.form; R->NQ = res_nq(cm->stats[CS_MAX_CHUNKS]); R->rg = cm->rg; R->per_cu = c.places / ctx->num_cus;
     R->next_seq = 0;
-    if (int r = res_variant_rg(ctx, R, rg, a, form_shmem(K), K, nq, true, &places)) return r;
+    int places = 0;
+    if (int r = res_variant_rg(ctx, R, cm->rg, a, c.shmem, c.form, R->NQ, true, &places)) return r;
     R->running = true;
     ++R->launches;
-    // every workgroup has to be ON the device: one that waits for a place would only start when the others leave.  The occupancy
-    // the API reports can be one more than the hardware admits (SGPR granules: MI355X_MICROARCH.md, "Residency"), so look.
-    const uint64_t t0 = res_now_ns();
-    while (R->h->up < (uint32_t)grid - 1u && !R->h->exited) {
-        if (res_now_ns() - t0 > 50000000ull) {                        // 50 ms
-            const uint32_t up = R->h->up;
-            if (int r = res_drain(ctx, R, true)) return r;
-            if (R->shrink >= 6) return ctx->fail(BK_E_HIP, "resident apply: only %u of %d workgroups became resident", up, grid);
-            ++R->shrink;
-            return res_launch(ctx, R, shape_tries, force_rg);
-        }
-    }
-    return BK_OK;
+    bool resident = false;
+    if (int r = res_await_residency(ctx, R, &resident)) return r;
+    return resident ? BK_OK : res_launch(ctx, R, shape_tries, force_rg);
 }
-
-static Resident *res_get(bk_ctx *ctx) { return ctx->resident; }
 
 // the device copies of the command ring: fine-grained device memory the host can write through the BAR when the device has a large one
 // (direct submission); else plain device memory fed by the relay wave
@@ -1184,7 +992,7 @@ int resident_wait(bk_ctx *ctx, uint64_t ticket, double *gpu_us);
 
 int resident_submit(bk_ctx *ctx, int frame, uint8_t *dst_first_owned_row, int dst_pitch, uint64_t *ticket)
 {
-    Resident *R = res_get(ctx);
+    Resident *R = ctx->resident;
     if (!R) return ctx->fail(BK_E_STATE, "bk_apply_resident_submit without bk_apply_resident_begin");
     res_retire(R);
     if (R->pending.size() >= (size_t)BK_RES_RING / 2) {                 // keep half the ring free: wait for the oldest
@@ -1199,7 +1007,7 @@ int resident_submit(bk_ctx *ctx, int frame, uint8_t *dst_first_owned_row, int ds
 
 int resident_wait(bk_ctx *ctx, uint64_t ticket, double *gpu_us)
 {
-    Resident *R = res_get(ctx);
+    Resident *R = ctx->resident;
     if (!R) return ctx->fail(BK_E_STATE, "bk_apply_resident_wait without bk_apply_resident_begin");
     if (ticket > R->base + R->next_seq) return ctx->fail(BK_E_INVALID, "bk_apply_resident_wait: no such ticket");
     if (ticket >= R->lost_lo && ticket <= R->lost_hi)
@@ -1237,7 +1045,7 @@ int resident_wait(bk_ctx *ctx, uint64_t ticket, double *gpu_us)
 // leave: the kernel exits, the context is back to launches per call
 int resident_stop(bk_ctx *ctx)
 {
-    Resident *R = res_get(ctx);
+    Resident *R = ctx->resident;
     if (!R) return BK_OK;
     int rc = BK_OK;
     res_retire(R);
@@ -1271,31 +1079,8 @@ int resident_stop(bk_ctx *ctx)
                     if ((raw[i] & 0x7FFFFFFFu) == mx0) R->streamed_argmax = (int)i;
                     R->streamed_many += (raw[i] & 0x7FFFFFFFu) * 2 > mx0 ? 1 : 0;
                 }
-            if (g_debug.print_model) {
-                if (FILE *df = fopen("gpurun_out/res_wg_stats.txt", "w")) {          // (developer: every workgroup's figure + its blocks' chunks / lines)
-                    for (size_t i = 0; i < raw.size(); ++i) {
-                        if (!(raw[i] & 0x80000000u)) continue;
-                        fprintf(df, "%zu %u", i, raw[i] & 0x7FFFFFFFu);
-                        for (int k = 0; k < R->depth; ++k) { const int v = R->plan_assign[i * R->depth + k]; if (v >= 0) fprintf(df, " %d:%u:%u", v, R->plan_hdr_chunks[(size_t)v], R->plan_lines[(size_t)v]); }
-                        fprintf(df, "\n");
-                    }
-                    fclose(df);
-                }
-                fprintf(stderr, "RESIDENT laggards (workgroup:streamed frames[chunks of its blocks]):");
-                int shown = 0;
-                std::vector<uint32_t> sorted_vals = st;
-                std::sort(sorted_vals.begin(), sorted_vals.end());
-                const uint32_t cut = sorted_vals.size() > 16 ? sorted_vals[sorted_vals.size() - 16] : 0;
-                for (size_t i = 0; i < raw.size() && shown < 24; ++i)
-                    if ((raw[i] & 0x80000000u) && (raw[i] & 0x7FFFFFFFu) >= cut) {
-                        fprintf(stderr, " %zu:%u[", i, raw[i] & 0x7FFFFFFFu);
-                        for (int k = 0; k < R->depth; ++k) { const int v = R->plan_assign[i * R->depth + k]; if (v >= 0) fprintf(stderr, "%u/%u ", R->plan_hdr_chunks[(size_t)v], R->plan_lines[(size_t)v]); }
-                        fprintf(stderr, "]");
-                        ++shown;
-                    }
-                fprintf(stderr, "\n");
-            }
             std::sort(st.begin(), st.end());
+            if (g_debug.print_model) res_print_laggards(R, raw, st);
             R->streamed_min = (int)st.front(); R->streamed_med = (int)st[st.size() / 2]; R->streamed_max = (int)st.back();
         }
     }
@@ -1324,7 +1109,7 @@ bool resident_leaves_room(bk_ctx *ctx) { Resident *R = ctx->resident; return ctx
 
 int resident_info(bk_ctx *ctx, int out[12])
 {
-    Resident *R = res_get(ctx);
+    Resident *R = ctx->resident;
     for (int i = 0; i < 12; ++i) out[i] = 0;
     if (!R) return BK_OK;
     out[0] = R->running && !R->h->exited ? 1 : 0; out[1] = R->nwg; out[2] = R->K; out[3] = R->NQ; out[4] = 8 * R->rg; out[5] = R->per_cu;

@@ -1,6 +1,7 @@
-"""The two host units of libblinkyhip that stand alone - the worker pool (bk_hostpool.cpp) and the code cache's trust checks
-(bk_codecache.cpp) - each linked into a small program of its own (tests/host/pool_check.cpp, codecache_check.cpp; built by
-tests/host/Makefile's `all`).  The programs print what failed and exit non-zero."""
+"""The three host units of libblinkyhip that stand alone - the worker pool (bk_hostpool.cpp), the code cache's trust checks
+(bk_codecache.cpp) and the resident apply's planner (bk_resident_plan.cpp) - each linked into a small program of its own
+(tests/host/pool_check.cpp, codecache_check.cpp, resplan_check.cpp; built by tests/host/Makefile's `all`).  The programs print what
+failed and exit non-zero."""
 import os
 import subprocess
 
@@ -33,3 +34,9 @@ def test_worker_pool(threads):
 def test_code_cache_trust():
     """SHA-256 vectors, sealed-file round trip, and every kind of file or directory that must be a miss"""
     _run("codecache_check")
+
+
+def test_resident_planner():
+    """every plan that fits holds what the resident kernel and its collector rely on, over a seeded sweep of block maps; the stride
+    planner refuses a plan with an empty stride group; the form choice takes each rung only when the rungs before it do not fit"""
+    assert "resplan_check ok" in _run("resplan_check")
