@@ -125,11 +125,22 @@ static void free_plate_slots(bk_ctx *ctx)
     ctx->plate_slot_bytes = 0;
 }
 
+// the mip pyramid (bk_apply_rgba_fb_trilinear_device); the caller has waited for the stream
+static void mip_free(bk_ctx *ctx)
+{
+    if (ctx->d_mip) (void)hipFree(ctx->d_mip);
+    ctx->d_mip = nullptr;
+    ctx->mip_ps = ctx->mip_levels = 0;
+    ctx->mip_made = false;
+    ctx->mip_plate_stride = 0;
+}
+
 static void free_maps(bk_ctx *ctx)
 {
     hipFree(ctx->d_offsets); ctx->d_offsets = nullptr;
     hipFree(ctx->d_tints); ctx->d_tints = nullptr;
     hipFree(ctx->d_subtexel); ctx->d_subtexel = nullptr;
+    hipFree(ctx->d_lod); ctx->d_lod = nullptr;
     hipFree(ctx->d_convert); ctx->d_convert = nullptr;
     hipFree(ctx->d_frame); ctx->d_frame = nullptr;
     hipFree(ctx->d_mask); ctx->d_mask = nullptr;
@@ -157,6 +168,7 @@ extern "C" void bk_destroy(bk_ctx *ctx)
     ctx->lut_rgba.free();
     ctx->lut_fb.free();
     hipFree(ctx->d_seam);
+    mip_free(ctx);
     hipFree(ctx->d_display);
     hipFree(ctx->d_flag_list);
     for (void *q : ctx->fwd_scratch) hipFree(q);
@@ -234,6 +246,7 @@ void bk::empty_context(bk_ctx *ctx)
     (void)hipFree(ctx->d_plate_stage); ctx->d_plate_stage = nullptr;
     (void)hipFree(ctx->d_rgba_stage); ctx->d_rgba_stage = nullptr; ctx->rgba_stage_bytes = 0;
     bk::footprint_free(ctx);
+    mip_free(ctx);
     ctx->W = ctx->H = ctx->ps = ctx->gp = ctx->ph = 0;
     ctx->row0 = ctx->row1 = 0;
     bk::lensmap_dropped(ctx);
@@ -273,6 +286,7 @@ extern "C" int bk_resize(bk_ctx *ctx, int width, int height)
     bk::lensmap_dropped(ctx);                               // (also when alloc_maps below keeps the buffers: the same pixel count)
     bk::seam_drop(ctx);                                     // (made for the platesize that was; a caller-set one goes with it)
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail_empty(ctx->fail(BK_E_HIP, "bk_resize: hipStreamSynchronize failed"));
+    if (ps != ctx->mip_ps) mip_free(ctx);                   // (a pyramid is kept across a resize that keeps the platesize)
     (void)hipFree(ctx->d_plate_stage);
     ctx->d_plate_stage = nullptr;
     free_plate_slots(ctx);                                  // (sized for the old platesize; re-created on the next async upload)
@@ -471,6 +485,7 @@ extern "C" int bk_set_subtexel(bk_ctx *ctx, int on)
         ctx->d_subtexel = nullptr;
     }
     if (!on) ctx->subtexel_valid = false;
+    if (ctx->subtexel_on != (on != 0)) bk::lod_invalidate(ctx);      // (the switch as it stands changes nothing: a set plane holds)
     ctx->subtexel_on = on != 0;
     return BK_OK;
 }
@@ -497,6 +512,7 @@ extern "C" int bk_set_lensmap_subtexel(bk_ctx *ctx, const uint16_t *sub)
     BK_HIP(ctx, hipMemcpyAsync(ctx->d_subtexel, sub, (size_t)ctx->W * ctx->rows() * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
     BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->subtexel_valid = true;
+    bk::lod_invalidate(ctx);
     return BK_OK;
 }
 
@@ -1022,6 +1038,173 @@ extern "C" int bk_apply_rgba_fb_bilinear_seams_device(bk_ctx *ctx, const void *c
                                                       void *dst_dev, int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256])
 {
     return fb_apply(ctx, "bk_apply_rgba_fb_bilinear_seams_device", bk::FB_BILINEAR_SEAMS, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, lut, 0);
+}
+
+// ---- trilinear: the mip pyramid, the level-of-detail plane and their apply (bk_apply_rgba_mip.inc) -------------------------------
+// the pyramid's layout for platesize ps into ctx->mip_table / mip_levels / mip_plate_stride: pitches multiples of 16, offsets of 128
+static void mip_layout(bk_ctx *ctx, int ps)
+{
+    memset(ctx->mip_table, 0, sizeof ctx->mip_table);
+    const int L = bk::mip_level_count(ps);
+    size_t at = 0;
+    int s = ps;
+    for (int k = 0; k < L; ++k, s = (s + 1) / 2) {
+        const uint32_t pitch = k ? ((uint32_t)s * 4u + 15u) & ~15u : 0u;
+        ctx->mip_table[k][0] = (uint32_t)at; ctx->mip_table[k][1] = pitch; ctx->mip_table[k][2] = (uint32_t)s - 1u; ctx->mip_table[k][3] = (uint32_t)s;
+        at = (at + (size_t)pitch * s + 127u) & ~(size_t)127u;      // (below 2^32: a third of 4 * ps^2 and ps < 2^15)
+    }
+    ctx->mip_levels = L;
+    ctx->mip_plate_stride = at;
+}
+
+extern "C" int bk_mip_info(bk_ctx *ctx, int *levels, int sizes[BK_MIP_MAX_LEVELS])
+{
+    if (!ctx || !levels || !sizes) return BK_E_INVALID;
+    if (ctx->ps < 1) return ctx->fail(BK_E_STATE, "bk_mip_info: no size (bk_resize first)");
+    *levels = bk::mip_level_count(ctx->ps);
+    int s = ctx->ps;
+    for (int k = 0; k < BK_MIP_MAX_LEVELS; ++k, s = (s + 1) / 2) sizes[k] = k < *levels ? s : 0;
+    return BK_OK;
+}
+
+// d_mip for the platesize in place, allocated (levels zeroed, the table uploaded) if it is not there
+static int mip_alloc(bk_ctx *ctx)
+{
+    if (ctx->d_mip && ctx->mip_ps == ctx->ps) return BK_OK;
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    mip_free(ctx);
+    mip_layout(ctx, ctx->ps);
+    const size_t bytes = BK_MIP_TABLE_BYTES + (size_t)BK_MAX_PLATES * ctx->mip_plate_stride;
+    if (hipMalloc((void **)&ctx->d_mip, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->d_mip = nullptr;
+        return ctx->fail(BK_E_NOMEM, "bk_apply_rgba_fb_trilinear_device: out of device memory (the mip pyramid, %zu bytes)", bytes);
+    }
+    static_assert(sizeof ctx->mip_table == BK_MIP_TABLE_BYTES, "the table is uint4 [BK_MIP_MAX_LEVELS]");
+    BK_HIP(ctx, hipMemsetAsync(ctx->d_mip, 0, bytes, ctx->stream));
+    BK_HIP(ctx, hipMemcpyAsync(ctx->d_mip, ctx->mip_table, BK_MIP_TABLE_BYTES, hipMemcpyHostToDevice, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->mip_ps = ctx->ps;
+    return BK_OK;
+}
+
+extern "C" int bk_read_mip_level(bk_ctx *ctx, int plate, int level, void *dst_host, int dst_pitch)
+{
+    if (!ctx || !dst_host) return BK_E_INVALID;
+    if (ctx->device < 0) return ctx->fail(BK_E_STATE, "bk_read_mip_level: this context was created without a device (BK_DEVICE_NONE)");
+    if (ctx->ps < 1 || !ctx->d_mip || ctx->mip_ps != ctx->ps || !ctx->mip_made)
+        return ctx->fail(BK_E_STATE, "bk_read_mip_level: no pyramid has been made for this platesize (bk_apply_rgba_fb_trilinear_device with mips = 1)");
+    if (plate < 0 || plate >= BK_MAX_PLATES || level < 1 || level >= ctx->mip_levels)
+        return ctx->fail(BK_E_INVALID, "bk_read_mip_level: plate %d, level %d (plates 0..5, levels 1..%d)", plate, level, ctx->mip_levels - 1);
+    const uint32_t *e = ctx->mip_table[level];
+    if ((long long)dst_pitch < 4ll * e[3]) return ctx->fail(BK_E_INVALID, "bk_read_mip_level: pitch %d below 4 * %u", dst_pitch, e[3]);
+    if (int r = ensure_device(ctx)) return r;
+    const uint8_t *src = ctx->d_mip + BK_MIP_TABLE_BYTES + (size_t)plate * ctx->mip_plate_stride + e[0];
+    BK_HIP(ctx, hipMemcpy2DAsync(dst_host, (size_t)dst_pitch, src, e[1], (size_t)e[3] * 4u, e[3], hipMemcpyDeviceToHost, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BK_OK;
+}
+
+extern "C" int bk_set_lod_bias(bk_ctx *ctx, int bias)
+{
+    if (!ctx) return BK_E_INVALID;
+    if (bias != ctx->lod_bias) bk::lod_invalidate(ctx);
+    ctx->lod_bias = bias;
+    return BK_OK;
+}
+
+// what the plane's three users check alike, up to the device being current and d_lod being there
+static int lod_args(bk_ctx *ctx, const char *who)
+{
+    if (ctx->device < 0) return ctx->fail(BK_E_STATE, "%s: this context was created without a device (BK_DEVICE_NONE)", who);
+    if (!ctx->lensmap_valid || !ctx->d_offsets) return ctx->fail(BK_E_STATE, "%s: no lensmap (bk_build / bk_set_lensmap first)", who);
+    if (!ctx->subtexel_valid || !ctx->d_subtexel)
+        return ctx->fail(BK_E_STATE, "%s: the lensmap has no sub-texel plane (bk_set_subtexel(ctx, 1), then bk_build / bk_set_lensmap)", who);
+    if (int r = ensure_device(ctx)) return r;
+    if (!ctx->d_lod) {
+        if (hipMalloc((void **)&ctx->d_lod, ctx->map_px * sizeof(uint16_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->d_lod = nullptr;
+            return ctx->fail(BK_E_NOMEM, "%s: out of device memory (the level-of-detail plane, %zu bytes)", who, ctx->map_px * sizeof(uint16_t));
+        }
+        ctx->lod_state = 0;
+    }
+    return BK_OK;
+}
+
+// the plane in place describes the lensmap: derived now unless it is current or was set by the caller
+static int lod_ready(bk_ctx *ctx, const char *who)
+{
+    if (int r = lod_args(ctx, who)) return r;
+    if (ctx->lod_state) return BK_OK;
+    if (int r = bk::launch_lod(ctx)) return r;
+    ctx->lod_state = 1;
+    return BK_OK;
+}
+
+extern "C" int bk_read_lod(bk_ctx *ctx, uint16_t *out)
+{
+    if (!ctx || !out) return BK_E_INVALID;
+    if (int r = lod_ready(ctx, "bk_read_lod")) return r;
+    BK_HIP(ctx, hipMemcpyAsync(out, ctx->d_lod, (size_t)ctx->W * ctx->rows() * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BK_OK;
+}
+
+extern "C" int bk_set_lensmap_lod(bk_ctx *ctx, const uint16_t *lod)
+{
+    if (!ctx || !lod) return BK_E_INVALID;
+    if (int r = lod_args(ctx, "bk_set_lensmap_lod")) return r;
+    const size_t px = (size_t)ctx->W * ctx->rows();
+    const unsigned top = (unsigned)(bk::mip_level_count(ctx->ps) - 1) * 256u;
+    for (size_t i = 0; i < px; ++i)
+        if (lod[i] > top) return ctx->fail(BK_E_INVALID, "bk_set_lensmap_lod: entry %zu (%u) is above (levels - 1) * 256 = %u", i, (unsigned)lod[i], top);
+    BK_HIP(ctx, hipMemcpyAsync(ctx->d_lod, lod, px * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+    BK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->lod_state = 2;
+    return BK_OK;
+}
+
+#if BK_DEBUG_API
+// the pyramid by itself (tools/bench_rgba.py --fb --trilinear times it): what mips = 1 does in front of the apply, and nothing else
+extern "C" int bk_debug_mip_pyramid(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES])
+{
+    if (!ctx || !plates_dev || !plate_pitch_bytes) return BK_E_INVALID;
+    if (ctx->device < 0) return ctx->fail(BK_E_STATE, "bk_debug_mip_pyramid: this context was created without a device (BK_DEVICE_NONE)");
+    if (ctx->ps < 1) return ctx->fail(BK_E_STATE, "bk_debug_mip_pyramid: no size (bk_resize first)");
+    for (int p = 0; p < BK_MAX_PLATES; ++p)
+        if (plates_dev[p] && ((((uintptr_t)plates_dev[p] | (uintptr_t)plate_pitch_bytes[p]) & 3u) || (long long)plate_pitch_bytes[p] < 4ll * ctx->ps))
+            return ctx->fail(BK_E_INVALID, "bk_debug_mip_pyramid: plate %d: the address and the pitch (%d) must be multiples of 4 bytes, the pitch at least 4 * %d", p,
+                             plate_pitch_bytes[p], ctx->ps);
+    if (int r = ensure_device(ctx)) return r;
+    if (int r = mip_alloc(ctx)) return r;
+    if (int r = bk::launch_mip_pyramid(ctx, plates_dev, plate_pitch_bytes)) return r;
+    ctx->mip_made = true;
+    return BK_OK;
+}
+#endif
+
+extern "C" int bk_apply_rgba_fb_trilinear_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
+                                                 void *dst_dev, int dst_pitch, int x0, int y0, const uint8_t lut[4][BK_MAX_PLATES][256], int mips)
+{
+    const char *who = "bk_apply_rgba_fb_trilinear_device";
+    if (int r = fb_apply_args(ctx, who, plates_dev, plate_pitch_bytes, dst_dev, dst_pitch, x0, y0, 0)) return r;
+    if (mips != 0 && mips != 1) return ctx->fail(BK_E_INVALID, "%s: mips is 0 or 1, not %d", who, mips);
+    if (!ctx->subtexel_valid || !ctx->d_subtexel)
+        return ctx->fail(BK_E_STATE, "%s: the lensmap has no sub-texel plane (bk_set_subtexel(ctx, 1), then bk_build / bk_set_lensmap)", who);
+    if (!mips && (!ctx->d_mip || ctx->mip_ps != ctx->ps || !ctx->mip_made))
+        return ctx->fail(BK_E_STATE, "%s: mips = 0, but no pyramid has been made for platesize %d (call with mips = 1 first)", who, ctx->ps);
+    if (int r = lod_ready(ctx, who)) return r;
+    bk::Range range(who);
+    if (mips) {
+        if (int r = mip_alloc(ctx)) return r;
+        if (int r = bk::launch_mip_pyramid(ctx, plates_dev, plate_pitch_bytes)) return r;
+        ctx->mip_made = true;
+    }
+    if (lut)
+        if (int r = upload_lut(ctx, ctx->lut_fb, lut)) return r;
+    uint8_t *first = (uint8_t *)dst_dev + (size_t)(y0 + ctx->row0) * dst_pitch + (size_t)x0 * 4;
+    return bk::launch_apply_rgba_fb_trilinear(ctx, plates_dev, plate_pitch_bytes, first, dst_pitch, lut ? ctx->lut_fb.d : nullptr);
 }
 
 // ---- resident single-frame apply (bk_apply_resident.inc) ------------------------------------------------------------

@@ -1744,5 +1744,6 @@ int coopmap_stats(bk_ctx *ctx, int out[6])
 #include "bk_apply_rgba.inc"
 #include "bk_apply_rgba_fb.inc"
 #include "bk_apply_resident.inc"
+#include "bk_apply_rgba_mip.inc"
 
 }  // namespace bk

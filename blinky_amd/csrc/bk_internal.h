@@ -121,6 +121,20 @@ struct bk_ctx {
     uint2 *d_seam = nullptr;
     size_t d_seam_words = 0;
     bool d_seam_current = false;
+    // the trilinear frame-buffer apply (bk_apply_rgba_mip.inc).  d_lod: the level-of-detail plane, uint16 [row1-row0][W] = level << 8 | fraction,
+    // beside the maps (map_px entries; freed with them), allocated by the first bk_read_lod / bk_set_lensmap_lod / trilinear apply;
+    // lod_state: 0 = to be derived, 1 = derived, 2 = set by the caller - back to 0 (bk::lod_invalidate) whenever the lensmap, the
+    // sub-texel plane, the owned rows or lod_bias change; never touched by a build.
+    // d_mip: the table (BK_MIP_TABLE_BYTES: mip_table as uint4 [16]) and levels 1 .. mip_levels - 1 of the six plates, mip_plate_stride bytes
+    // each, for platesize mip_ps; allocated by the first trilinear apply with mips = 1, freed by a bk_resize that changes ps and by
+    // bk_destroy; mip_made: that pyramid has been filled at least once
+    uint16_t *d_lod = nullptr;
+    int lod_state = 0, lod_bias = 0;
+    uint8_t *d_mip = nullptr;
+    int mip_ps = 0, mip_levels = 0;
+    bool mip_made = false;
+    size_t mip_plate_stride = 0;
+    uint32_t mip_table[BK_MIP_MAX_LEVELS][4] = {};      // {byte offset inside a plate's part, row pitch, s_k - 1, s_k}
     uint8_t *d_frame = nullptr;      // [row1-row0][W] staging for bk_apply (host dst)
     bk::LutCopy pal;                 // [6][256] the 8-bit palette (upload_pal); its buffer is there from bk_create on
     bk::LutCopy lut_rgba;            // [4][6][256] the byte LUTs of bk_apply_rgba_tinted_device / _ss2_device (pal stays the 8-bit palette)
@@ -259,7 +273,8 @@ void coopmap_invalidate(bk_ctx *ctx);
 // (coopmap_invalidate ends a resident session and takes a context with no block map, or no device, as it is)
 // the entries in place changed, the plane (if valid) with them: bk_truncate_build, whose pass writes the plane only while it is
 // valid - so the plane's flag is not lensmap_replaced's formula there
-inline void lensmap_edited(bk_ctx *ctx) { ctx->spans_valid = false; coopmap_invalidate(ctx); footprint_invalidate(ctx); }
+inline void lod_invalidate(bk_ctx *ctx) { ctx->lod_state = 0; }      // the level-of-detail plane, a caller-set one too, no longer describes the lensmap
+inline void lensmap_edited(bk_ctx *ctx) { ctx->spans_valid = false; coopmap_invalidate(ctx); footprint_invalidate(ctx); lod_invalidate(ctx); }
 // there is no table now (free_maps, empty_context, bk_resize, bk_set_rows): every consumer answers BK_E_STATE until there is one
 inline void lensmap_dropped(bk_ctx *ctx) { ctx->lensmap_valid = ctx->subtexel_valid = false; lensmap_edited(ctx); }
 // the table in place is new (bk_set_lensmap; bk_build, in front of every way out); its plane, where there is one, was written with it
@@ -278,6 +293,14 @@ int launch_apply_rgba(bk_ctx *ctx, int globe0, int nframes, uint8_t *dst_first_o
 enum FbMode { FB_NEAREST, FB_SS2, FB_BILINEAR, FB_BILINEAR_SEAMS };
 int launch_apply_rgba_fb(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
                          const uint8_t *d_lut, FbMode mode);
+// bk_apply_rgba_mip.inc (part of bk_apply_coop.hip): the mip pyramid of six frame-buffer plates, the level-of-detail plane and the trilinear apply
+#define BK_MIP_TABLE_BYTES 256      // uint4 [BK_MIP_MAX_LEVELS] in front of the pyramid
+// levels of a platesize: s_0 = ps, s_{k+1} = (s_k + 1) / 2 down to 1 (0 for ps < 1; at most BK_MIP_MAX_LEVELS for every ps bk_resize accepts)
+inline int mip_level_count(int ps) { int n = 0; for (int s = ps; s >= 1; s = (s + 1) / 2) { ++n; if (s == 1) break; } return n; }
+int launch_mip_pyramid(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES]);
+int launch_lod(bk_ctx *ctx);
+int launch_apply_rgba_fb_trilinear(bk_ctx *ctx, const void *const plates[BK_MAX_PLATES], const int pitches[BK_MAX_PLATES], uint8_t *dst, int dst_pitch,
+                                   const uint8_t *d_lut);
 int coopmap_stats(bk_ctx *ctx, int out[6]);   // blocks, direct-gather blocks, empty blocks, LDS bytes per buffer
 int coopmap_traffic_model(bk_ctx *ctx, uint64_t out[8]);
 int coopmap_xcd_probe(bk_ctx *ctx, int *out, int nwg);

@@ -21,6 +21,7 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH)
 
 MAX_PLATES = 6
+MIP_MAX_LEVELS = 16
 NULL_OFFSET = 0xFFFFFFFF
 DEVICE_NONE = -2
 OK = 0
@@ -87,9 +88,16 @@ _SIGS = {
     "bk_apply_rgba_fb_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp, _i]),
     "bk_apply_rgba_fb_bilinear_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp]),
     "bk_apply_rgba_fb_bilinear_seams_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp]),
+    "bk_apply_rgba_fb_trilinear_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _i, _vp, _i]),
+    "bk_mip_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "bk_read_mip_level": (_i, [_vp, _i, _i, _vp, _i]),
+    "bk_set_lod_bias": (_i, [_vp, _i]),
+    "bk_read_lod": (_i, [_vp, _vp]),
+    "bk_set_lensmap_lod": (_i, [_vp, _vp]),
     "bk_read_seam_table": (_i, [_vp, _vp]),
     "bk_set_seam_table": (_i, [_vp, _vp]),
     "bk_debug_fb_decode_check": (C.c_longlong, [_i, _i]),
+    "bk_debug_mip_pyramid": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i)]),
     "bk_globe_device_ptr": (_vp, [_vp, _i]),
     "bk_fill_plate_lcg": (_i, [_vp, _i, _i, C.c_uint32]),
     "bk_apply": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
@@ -568,6 +576,51 @@ class Context:
         pp, pi = _fb_plates(plates, pitches)
         lut = _lut(lut)
         self._chk(lib.bk_apply_rgba_fb_bilinear_seams_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut)))
+
+    def apply_rgba_fb_trilinear_device(self, plates, pitches, dst_ptr, dst_pitch, x0=0, y0=0, lut=None, mips=True):
+        """apply_rgba_fb_bilinear_device blended between two levels of a mip pyramid of the plates, chosen per pixel by the level-of-detail
+        plane (read_lod): the answer to minification.  mips True: the pyramid is made from these plates first, on the same stream; False:
+        the pyramid as last made is used.  Each of the eight texels goes through the pixel's tint before any blend"""
+        pp, pi = _fb_plates(plates, pitches)
+        lut = _lut(lut)
+        self._chk(lib.bk_apply_rgba_fb_trilinear_device(self._h, pp, pi, dst_ptr, dst_pitch, x0, y0, _ptr(lut), int(mips)))
+
+    def debug_mip_pyramid(self, plates, pitches):
+        """the mip pyramid of apply_rgba_fb_trilinear_device by itself (bk_debug_mip_pyramid): the two launches, no apply"""
+        pp, pi = _fb_plates(plates, pitches)
+        self._chk(lib.bk_debug_mip_pyramid(self._h, pp, pi))
+
+    def mip_info(self):
+        """the sizes s_0 = ps, s_1, ... 1 of the mip pyramid's levels for the size in place"""
+        n, sizes = _i(), (_i * MIP_MAX_LEVELS)()
+        self._chk(lib.bk_mip_info(self._h, C.byref(n), sizes))
+        return list(sizes)[:n.value]
+
+    def read_mip_level(self, plate, level):
+        """uint8 [s][s][4]: level 1 <= level < len(mip_info()) of `plate` as the last trilinear apply with mips made it"""
+        s = self.mip_info()[level] if 0 <= level < len(self.mip_info()) else 1
+        out = np.empty((s, s, 4), np.uint8)
+        self._chk(lib.bk_read_mip_level(self._h, int(plate), int(level), _ptr(out), 4 * s))
+        return out
+
+    def set_lod_bias(self, bias):
+        """a signed bias in 1/256 level on every mapped pixel's level of detail; changing it drops the plane"""
+        self._chk(lib.bk_set_lod_bias(self._h, int(bias)))
+
+    def read_lod(self):
+        """the level-of-detail plane, uint16 [rows * W] = level << 8 | fraction, derived on the device if it is not current"""
+        w, h, ps, r0, r1 = self.size()
+        lod = np.empty((r1 - r0) * w, np.uint16)
+        self._chk(lib.bk_read_lod(self._h, _ptr(lod)))
+        return lod
+
+    def set_lensmap_lod(self, lod):
+        """replace the level-of-detail plane until the lensmap, the sub-texel plane, the owned rows or the bias change"""
+        w, h, ps, r0, r1 = self.size()
+        lod = np.ascontiguousarray(lod, dtype=np.uint16).reshape(-1)
+        if lod.size != (r1 - r0) * w:
+            raise ValueError(f"lod must have {(r1 - r0) * w} entries, not {lod.size}")
+        self._chk(lib.bk_set_lensmap_lod(self._h, _ptr(lod)))
 
     def read_seam_table(self):
         """uint32 [6][4][ps + 2], reference layout, 0xFFFFFFFF = none: the texel that stands in for the virtual texel one step outside plate

@@ -449,6 +449,68 @@ int bk_apply_rgba_fb_bilinear_seams_device(bk_ctx *ctx, const void *const plates
                                            void *dst_dev, int dst_pitch, int x0, int y0,
                                            const uint8_t lut[4][BK_MAX_PLATES][256] /* nullable: NULL = plain, else tinted */);
 
+/* ---- TRILINEAR: a mip pyramid of the plates and a per-pixel level of detail - the answer to MINIFICATION -----------------------------
+ * A whole-globe lens minifies everywhere (a 4K hammer frame: about 2.25 texels a pixel in each direction); nearest and bilinear sampling
+ * then keep one texel in five.  bk_apply_rgba_fb_trilinear_device blends two levels of a pyramid of the caller's plates, chosen per
+ * pixel by a level-of-detail plane derived from the lensmap and the sub-texel plane.  Everything is integer arithmetic and exact.
+ * THE PYRAMID.  Level 0 is the caller's plate, s_0 = ps; s_{k+1} = (s_k + 1) / 2 down to s_{L-1} = 1 (L = 1, 2, 3, 4, 5, 7, 9, 13, 16 for
+ * ps = 1, 2, 3, 5, 16, 33, 203, 2160, 26752; at most BK_MIP_MAX_LEVELS).  Texel (x, y) of level k + 1, per byte: (a + b + c + d + 2) >> 2
+ * over level k's texels (2x, 2y), (2x + 1, 2y), (2x, 2y + 1), (2x + 1, 2y + 1), coordinates clamped to s_k - 1 (an odd size repeats its
+ * last row and column); every level is made from the ROUNDED level below.  Levels 1 .. L - 1 of all six plates live in memory of the
+ * context (about a third of 6 * 4 * ps^2 bytes: 37 MB at ps 2160), allocated by the first trilinear apply with mips = 1, freed by a
+ * bk_resize that changes the platesize and by bk_destroy; a context that never makes that call allocates nothing.  Making it reads EVERY
+ * texel of every non-NULL plate (two launches a frame); a NULL plate's levels stay as they were.
+ * bk_mip_info: *levels = L and sizes[k] = s_k for k < L (0 beyond) for the size in place; works without a device; BK_E_STATE without a size.
+ * bk_read_mip_level: level 1 <= level < L of `plate` as last made, s_k rows of 4 * s_k bytes dst_pitch apart, into host memory;
+ * synchronous.  BK_E_INVALID for a bad plate, level or pitch, BK_E_STATE while there is no pyramid for this platesize.
+ * THE LEVEL-OF-DETAIL PLANE: uint16 [row1 - row0][W] beside the lensmap, level << 8 | fraction (in 1/256 level).  For a mapped pixel with
+ * texel (px, py) on plate p and sub qx | qy << 8 the position is U = px * 256 + qx, V = py * 256 + qy.  Horizontal step: to the neighbour
+ * at x + 1 if that is inside the frame, mapped and on plate p; otherwise to x - 1 under the same test; otherwise none;
+ * dh = max(|dU|, |dV|) to that neighbour.  Vertical step dv: the same with y + 1, then y - 1, inside the OWNED rows.  rho = max(dh, dv),
+ * 0 with neither step.  rho <= 256: 0; otherwise k = floor(log2 rho) and (k - 8) * 256 + ((rho << 8) >> k) - 256 (the piecewise-linear
+ * log2: 257 -> 1, 511 -> 255, 512 -> 256, 768 -> 384).  Then the bias is added (to every mapped pixel's value) and the sum clamped to
+ * [0, (L - 1) * 256]; an unmapped pixel has 0.  A forward map's plane of 0x8080 gives differences of texel centres.
+ * STRIPES: a stripe context's plane differs from the whole frame's only where a row's vertical neighbour was taken on the other side -
+ * the stripe's last row, where that is not the frame's last (its step goes up instead of down).  A halo row is out of scope.
+ * bk_set_lod_bias: a signed bias in 1/256 level, default 0; changing it drops the plane.
+ * Life: derived on the device by the first trilinear apply or bk_read_lod after the lensmap, the sub-texel plane, the owned rows or the
+ * bias changed (bk_build, bk_set_lensmap, bk_set_lensmap_subtexel, bk_set_subtexel, bk_truncate_build, bk_set_rows, bk_resize);
+ * never by a build, and not allocated (2 bytes a pixel of the owned rows) before its first use.  bk_set_lensmap_lod replaces it, as
+ * bk_set_lensmap_subtexel replaces the sub-texel plane, until one of those events (bk_set_subtexel counts when it CHANGES the switch: setting it
+ * to what it is drops nothing); a value above (L - 1) * 256 is BK_E_INVALID.
+ * bk_read_lod copies it out, deriving it if needed.  Both answer BK_E_STATE without a lensmap, without a sub-texel plane and on a
+ * BK_DEVICE_NONE context. */
+#define BK_MIP_MAX_LEVELS 16
+int bk_mip_info(bk_ctx *ctx, int *levels, int sizes[BK_MIP_MAX_LEVELS]);
+int bk_read_mip_level(bk_ctx *ctx, int plate, int level, void *dst_host, int dst_pitch);
+int bk_set_lod_bias(bk_ctx *ctx, int bias);
+int bk_read_lod(bk_ctx *ctx, uint16_t *out);
+int bk_set_lensmap_lod(bk_ctx *ctx, const uint16_t *lod);
+/* bk_apply_rgba_fb_trilinear_device.  Sources, destination, origin, owned rows, untouched unmapped pixels, alignment classes, NULL plates
+ * and errors are bk_apply_rgba_fb_bilinear_device's.  mips = 1: the pyramid is made from these plates first, on the same stream;
+ * mips = 0: the pyramid as last made is used (BK_E_STATE if there is none for this platesize) - level 0 still comes from the plates
+ * given; any other value: BK_E_INVALID.
+ * Semantics per mapped pixel, lod its plane value: l = lod >> 8, fl = lod & 255; levels lo = l and hi = min(l + 1, L - 1).  At level k the
+ * position is Uk = U >> k, Vk = V >> k (level k's texel j covers level 0's [j * 2^k, (j + 1) * 2^k): the centre convention carries over),
+ * and (Uk >> 8, Uk & 255) are what (px, qx) are to bk_apply_rgba_fb_bilinear_device: sx = (Uk & 255) + 128, xa = (Uk >> 8) - 1 + (sx >> 8),
+ * fx = sx & 255, xb = xa + 1, both clamped to [0, s_k - 1] of the pixel's OWN plate (rows alike; no seams at any level).  Per byte and
+ * level the UNROUNDED v = h0 * (256 - fy) + h1 * fy (h0, h1 as there); out = (v_lo * (256 - fl) + v_hi * fl + 2^23) >> 24 - below 2^32
+ * throughout.  At fl = 0 that is (v_lo + 32768) >> 16: a plane of zeros gives bk_apply_rgba_fb_bilinear_device's frame byte for byte
+ * (and with subs of 0x8080 bk_apply_rgba_fb_device's); a constant plate gives its constant.  lut given: each of the EIGHT texels goes
+ * through the pixel's tint before any blend.
+ * Reads: level 0 within one texel of a named texel, clamped, as the bilinear call; pyramid texels of any level; also at weight 0.
+ * The first call after the plane's inputs changed derives the plane (one launch, no host wait); the first with mips = 1 for a platesize
+ * allocates the pyramid.
+ * Measured (tools/bench_rgba.py --fb --trilinear [--tint], profiles/rgba_fb_trilinear_apply.txt; 4K, plates from HBM): the pyramid by itself
+ * 65 - 74 us (149.3 MB at 2.03 TB/s on hammer: below the 2.87 TB/s of the footprint re-tile); the frame with mips = 0 against the bilinear
+ * call's: hammer 89.4 / 82.0 us, quincuncial 95.1 / 83.0, winkel2 99.5 / 82.9, panini - all of whose pixels blend level 0 with level 1 -
+ * 112.0 / 63.2.
+ * Out of scope: seams across plates at any level, ss2 combined with it, anisotropic footprints, a pyramid limited to the footprint, a halo
+ * row for stripes, the staged ring applies, the resident kernel, the bk_comm_* / bk_multi_* exchanges, the drop-in fisheye_hip.c. */
+int bk_apply_rgba_fb_trilinear_device(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES],
+                                      void *dst_dev, int dst_pitch, int x0, int y0,
+                                      const uint8_t lut[4][BK_MAX_PLATES][256] /* nullable: NULL = plain, else tinted */, int mips);
+
 /* ---- resident single-frame apply ------------------------------------------------------------------------------------
  * replaces: the per-frame call of render_lensmap (fisheye.c:803 -> 2406-2424) for hosts whose globes stay in device memory.
  * One bk_apply_device launch per frame re-reads the whole block map of the staged apply (2 bytes per pixel and more: half of a

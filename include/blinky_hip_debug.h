@@ -135,6 +135,9 @@ int         bk_debug_row_costs(bk_ctx *ctx, uint32_t *host_out);
  * and the first and last two tiles of every plate, where the comparisons decide.  -> the number of texels that decode differently
  * (0 = exact), -1 for a layout bk_resize does not accept (gp no multiple of 64, ph none of 8 or above gp, 6 * gp * ph >= 2^32 - 1) */
 long long   bk_debug_fb_decode_check(int gp, int ph);
+/* the mip pyramid of bk_apply_rgba_fb_trilinear_device by itself: what mips = 1 does in front of the apply (allocation on first use, the two
+ * launches on the context's stream) and no apply - for timing it alone.  Plates and pitches as that call's; a NULL plate is skipped */
+int         bk_debug_mip_pyramid(bk_ctx *ctx, const void *const plates_dev[BK_MAX_PLATES], const int plate_pitch_bytes[BK_MAX_PLATES]);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ At 3840x2160 cube/panini and cube/hammer, over the 64-slot LCG ring of the bench
 B's output is compared with A's plane by plane before anything is timed.  Timing: HIP events on the context's stream, warm-up
 launches first, regions of at least --region seconds made of ten event-timed trains of launches (a region's figure is the median
 train), A / B / A / B ... alternated --repeats times inside this one process.  The target: B's median <= A's median + A's own spread
-(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2] [--upload] [--fb [--bilinear [--seams]]]
+(max - min of A's region medians).  usage: python tools/bench_rgba.py [--lenses panini,hammer] [--repeats 5] [--out FILE] [--tint] [--ss2] [--upload] [--fb [--bilinear [--seams] | --trilinear]]
 
 --tint: the same protocol for f_rubix on truecolour frames, three launches alternated A' / B' / B:
   A'  one bk_apply_device launch of 64 8-bit frames with rubix_on = 1 (existing code: the same bytes through the same number of LUT
@@ -46,6 +46,9 @@ stay resident would pay).
   (bk_apply_rgba_fb_bilinear_seams_device with the cube's computed seam table), alternated frame by frame as below; S is held to the numpy
   model (tests/seam_model.py) at full size before anything is timed; the target is S <= L + the two spreads.  Also: the host cost of making
   the seam table at this platesize, without and with a globe_plate callback.
+--fb --trilinear [--tint] [--reps 31]: L (bk_apply_rgba_fb_bilinear_device, its kernel unchanged), T0 and T (bk_apply_rgba_fb_trilinear_device
+  without and with making the mip pyramid) and M (the pyramid by itself: bk_debug_mip_pyramid, its two launches and no apply), alternated
+  frame by frame as below; T is held to the numpy model of tests/trilinear_model.py at full size before anything is timed.
 --fb --bilinear [--tint] [--reps 31]: bilinear texel filtering against the nearest-texel launch it extends, alternated frame by frame:
   D  bk_apply_rgba_fb_device (--tint: with the tables) - existing code
   L  bk_apply_rgba_fb_bilinear_device from the same plates through the sub-texel plane the build kept (bk_set_subtexel)
@@ -630,6 +633,119 @@ def measure_fb_seams(lens, repeats, reps, tint):
                 s_over_l=med["s"] / med["l"], target_met=bool(med["s"] <= med["l"] + spread["l"] + spread["s"]))
 
 
+def measure_fb_trilinear(lens, repeats, reps, tint):
+    """L (bk_apply_rgba_fb_bilinear_device), T0 (bk_apply_rgba_fb_trilinear_device, mips = 0), T (mips = 1) and M (the pyramid by itself:
+    bk_debug_mip_pyramid, the two launches that mips = 1 puts in front of the apply and nothing else), frame by frame, from the ring of
+    measure_fb"""
+    import trilinear_model as TM
+    SETS = SLOTS // 4
+    stream = torch.cuda.current_stream()
+
+    ctx = blinky_amd.Context(0)
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_frames(1)
+    ctx.set_subtexel(True)
+    S.configure(ctx, "cube", lens, None, (W, H))
+    display, _ = ctx.build()
+    ps = min(W, H)
+    shown = [p for p in range(6) if p < len(display) and display[p]]
+    lut = None
+    if tint:
+        pal = blinky_amd.ffi.create_palmap(((np.arange(768) * 37) % 256).astype(np.uint8))
+        lut = np.ascontiguousarray(np.broadcast_to(pal, (4, 6, 256)))
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    src = [[torch.randint(0, 256, (ps, ps, 4), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(6)] for _ in range(SETS)]
+    pitch = 4 * ps
+    ptrs = [[src[s][p].data_ptr() if p in shown else None for p in range(6)] for s in range(SETS)]
+    pitches = [pitch] * 6
+    out = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")
+    plug = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+
+    def bilinear(s):
+        ctx.apply_rgba_fb_bilinear_device(ptrs[s], pitches, out.data_ptr(), 4 * W, lut=lut)
+
+    def tri0(s):
+        ctx.apply_rgba_fb_trilinear_device(ptrs[s], pitches, out.data_ptr(), 4 * W, lut=lut, mips=False)
+
+    def tri(s):
+        ctx.apply_rgba_fb_trilinear_device(ptrs[s], pitches, out.data_ptr(), 4 * W, lut=lut, mips=True)
+
+    def pyramid(s):
+        ctx.debug_mip_pyramid(ptrs[s], pitches)
+
+    # before anything is timed: T's frame is the numpy model's, at full size, in the flavour that is timed, and the plane the derivation's
+    off, tints = ctx.read_lensmap()
+    sub = ctx.read_subtexel()
+    lod = ctx.read_lod()
+    if not np.array_equal(lod, TM.derive_lod(off.reshape(-1), sub, W, H, ps)):
+        raise SystemExit(f"{lens}: the level-of-detail plane differs from the numpy derivation - nothing timed")
+    plates = np.stack([src[0][p].cpu().numpy() for p in range(6)])
+    pyr = TM.pyramid(plates)
+    pyr = [pyr[0]] + [np.where(np.isin(np.arange(6), shown)[:, None, None, None], level, 0) for level in pyr[1:]]
+    tri(0)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy().reshape(H, 4 * W)
+    want = np.zeros((H, 4 * W), np.uint8)
+    for r0 in range(0, H, 120):                            # (in bands: the model keeps a dozen int64 arrays a level)
+        r1 = min(H, r0 + 120)
+        TM.trilinear_frame(pyr, off.reshape(-1), sub, lod[r0 * W:r1 * W], tints.reshape(-1), W, H, ps, (r0, r1), lut, want, 0, 0)
+    if not np.array_equal(got, want):
+        raise SystemExit(f"{lens}: the trilinear frame differs from the numpy model in {int((got != want).sum())} bytes - nothing timed")
+    m = off.reshape(-1) != 0xFFFFFFFF
+    census = [int(((lod[m] >> 8) == k).sum()) for k in range(len(pyr))]
+    mapped, lod0 = int(m.sum()), int((lod[m] == 0).sum())
+    del off, tints, sub, plates, pyr, got, want
+    calls = [("l", bilinear), ("t0", tri0), ("t", tri), ("m", pyramid)]
+    for k in range(2 * SETS):
+        calls[k % 4][1](k % SETS)
+    torch.cuda.synchronize()
+    blocks = {n: [] for n, _ in calls}
+    k = 0
+    for _ in range(repeats):
+        ev = []
+        for r in range(4 * reps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            plug.fill_(r & 255)
+            e[0].record(stream)
+            calls[r % 4][1](k % SETS)
+            e[1].record(stream)
+            ev.append(e)
+            k += 1
+        torch.cuda.synchronize()
+        for i, (n, _) in enumerate(calls):
+            blocks[n].append(statistics.median(e[0].elapsed_time(e[1]) * 1e3 for e in ev[i::4]))
+    ctx.close()
+    med = {n: statistics.median(v) for n, v in blocks.items()}
+    spread = {n: max(v) - min(v) for n, v in blocks.items()}
+    moved = len(shown) * 4 * ps * ps * 4 // 3               # the pyramid's bytes: every shown plate read once, a third of that written
+    return dict(lens=lens, W=W, H=H, ps=ps, tint=bool(tint), trilinear=True, displayed_plates=shown, frames_per_block=reps, blocks=repeats,
+                mapped_pixels=mapped, pixels_at_lod_0=lod0, pixels_by_lower_level=census, blocks_us=blocks, median_us=med, spread_us=spread,
+                t0_over_l=med["t0"] / med["l"], t_minus_t0_us=med["t"] - med["t0"], pyramid_bytes=moved,
+                pyramid_gb_s=moved / (med["m"] * 1e-6) / 1e9)
+
+
+def main_fb_trilinear(args):
+    rows = []
+    what = "tinted" if args.tint else "plain"
+    for lens in args.lenses.split(","):
+        r = measure_fb_trilinear(lens, args.repeats, max(31, args.reps), args.tint)
+        rows.append(r)
+        m, s, b = r["median_us"], r["spread_us"], r["blocks_us"]
+        print(f"4K cube/{lens}, one {what} truecolour frame per call from device plates (a ring of 16 sets), plates {r['displayed_plates']} displayed, "
+              f"{r['mapped_pixels']} mapped pixels, {r['pixels_at_lod_0']} at lod 0, by lower level {r['pixels_by_lower_level']}, "
+              f"{r['blocks']} blocks of {r['frames_per_block']} frames each, L / T0 / T / M alternated:\n"
+              f"  L   bk_apply_rgba_fb_bilinear_device             {m['l']:8.1f} us (blocks {fmt(b['l'])}; spread {s['l']:.1f})\n"
+              f"  T0  bk_apply_rgba_fb_trilinear_device, mips = 0  {m['t0']:8.1f} us (blocks {fmt(b['t0'])}; spread {s['t0']:.1f})\n"
+              f"  T   bk_apply_rgba_fb_trilinear_device, mips = 1  {m['t']:8.1f} us (blocks {fmt(b['t'])}; spread {s['t']:.1f})\n"
+              f"  M   the pyramid by itself (bk_debug_mip_pyramid)  {m['m']:8.1f} us (blocks {fmt(b['m'])}; spread {s['m']:.1f})\n"
+              f"  T == the numpy model at full size; T0 / L = {r['t0_over_l']:.3f}; T - T0 = {r['t_minus_t0_us']:.1f} us; "
+              f"M moves {r['pyramid_bytes'] / 1e6:.1f} MB: {r['pyramid_gb_s']:.0f} GB/s", flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main_fb_seams(args):
     rows = []
     what = "tinted" if args.tint else "plain"
@@ -767,6 +883,7 @@ def main():
     ap.add_argument("--fb", action="store_true", help="one frame per call: footprint uploads + the staged one-frame apply B + P / bk_apply_rgba_fb_device D (with --tint / --ss2: the matching pairs)")
     ap.add_argument("--seams", action="store_true", help="with --fb --bilinear: bk_apply_rgba_fb_bilinear_device L / bk_apply_rgba_fb_bilinear_seams_device S, and the host cost of the seam table")
     ap.add_argument("--bilinear", action="store_true", help="with --fb: bk_apply_rgba_fb_device D / bk_apply_rgba_fb_bilinear_device L (with --tint: both through the tables), and bk_build with the sub-texel plane off / on")
+    ap.add_argument("--trilinear", action="store_true", help="with --fb: bk_apply_rgba_fb_bilinear_device L / bk_apply_rgba_fb_trilinear_device without (T0) and with (T) the pyramid / the pyramid alone M")
     ap.add_argument("--reps", type=int, default=31, help="--upload / --fb: frames each way per block (at least 31)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -775,6 +892,10 @@ def main():
         if not (args.fb and args.bilinear) or args.ss2:
             raise SystemExit("--seams goes with --fb --bilinear (and not with --ss2)")
         return main_fb_seams(args)
+    if args.trilinear:
+        if not args.fb or args.ss2 or args.bilinear or args.seams:
+            raise SystemExit("--trilinear goes with --fb (and not with --ss2, --bilinear or --seams)")
+        return main_fb_trilinear(args)
     if args.bilinear:
         if not args.fb or args.ss2:
             raise SystemExit("--bilinear goes with --fb (and not with --ss2)")
