@@ -67,10 +67,20 @@ def model(pyr, table, sub, lod, d, lut, rows=None):
     return want
 
 
-def check(ctx, table, sub, lod, plates, lut, what, layout="tight", rows=None, d=None, null_unread=False):
+def same(got, want, d, what):
+    """two whole destination allocations are equal; if not, the first differing byte as a pixel of the frame"""
+    if not np.array_equal(got, want):
+        at = int(np.flatnonzero(got != want)[0])
+        y, xb = divmod(at, d["pitch"])
+        raise AssertionError(f"{what}: {int((got != want).sum())} of {want.size} bytes differ, the first at pixel (x {xb // 4 - d['x0']}, y {y - d['y0']}) "
+                             f"byte {xb % 4}: {int(got[at])}, expected {int(want[at])}")
+
+
+def check(ctx, table, sub, lod, plates, lut, what, layout="tight", rows=None, d=None, null_unread=False, pyr=None):
+    """pyr: TM.pyramid(plates), where the caller has it already"""
     off, tints, W, H, ps = table
     d = d or FB.dest(W, H, False)
-    pyr = TM.pyramid(plates)
+    pyr = pyr or TM.pyramid(plates)
     _, mask = BL.guarded(plates, table, sub, 0, rows)
     skip = [p for p in range(6) if not mask[p].any()] if null_unread else ()
     dev, ptrs, pitches = FB.source(plates, layout, skip=skip)
@@ -78,14 +88,13 @@ def check(ctx, table, sub, lod, plates, lut, what, layout="tight", rows=None, d=
         pyr = [pyr[0]] + [np.where(np.isin(np.arange(6), skip)[:, None, None, None], 0, level) for level in pyr[1:]]
     for tinted in (False, True):
         got = run(ctx, ptrs, pitches, d, lut if tinted else None)
-        np.testing.assert_array_equal(got, model(pyr, table, sub, lod, d, lut if tinted else None, rows), err_msg=f"{what} tinted {tinted} mips 1")
+        same(got, model(pyr, table, sub, lod, d, lut if tinted else None, rows), d, f"{what} tinted {tinted} mips 1")
     for guard in BL.GUARDS:
         g, _ = BL.guarded(plates, table, sub, guard, rows)
         devg, ptrsg, pitchesg = FB.source(g, layout, skip=skip)
         for tinted in (False, True):
             got = run(ctx, ptrsg, pitchesg, d, lut if tinted else None, mips=False)
-            np.testing.assert_array_equal(got, model(pyr, table, sub, lod, d, lut if tinted else None, rows),
-                                          err_msg=f"{what} tinted {tinted} mips 0 guard {guard:#x}")
+            same(got, model(pyr, table, sub, lod, d, lut if tinted else None, rows), d, f"{what} tinted {tinted} mips 0 guard {guard:#x}")
 
 
 # ---- 1. drawn tables, planes set by hand ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """The trilinear apply without a GPU: the three models of tests/trilinear_model.py (pyramid, level of detail, frame) each against a second
 formulation in plain Python loops, the blend's identities, the level-of-detail derivation on host builds - the CONDITIONS that keep the
-GPU files from testing nothing - and the census of the drawn cases those files apply."""
+GPU files from testing nothing - and the census of the drawn cases those files apply; the same for the deep files (tests/test_*_deep_gpu.py,
+platesizes with 10 to 12 levels): the directed ramp against the pixel loop, and what the ramp and the deep stripes have to reach."""
 import numpy as np
 import pytest
 
@@ -216,3 +217,131 @@ def test_census_of_the_committed_apply_cases():
         refused += detail["other_plate"]
     assert ways["h"] == {1, -1, 0} and ways["v"] == {1, -1, 0}, ways
     assert refused > 0
+
+
+# ---- 5. depth: what tests/test_*_deep_gpu.py run - platesizes with 10 to 12 levels ------------------------------------------------------
+def test_the_deep_platesizes_reach_what_they_are_there_for():
+    """the arithmetic behind the comments of tests/test_mip_pyramid_deep_gpu.py's DEEP"""
+    import test_apply_rgba_fb_gpu as FB
+    import test_mip_pyramid_deep_gpu as MD
+    s = {ps: TM.level_sizes(ps) for ps in MD.DEEP}
+    assert sorted(MD.DEEP) == [129, 130, 257, 258, 260, 513, 640, 721, 1024, 1025] and set(MD.DEEP.values()) == set(FB.LAYOUTS)
+    assert [len(s[ps]) for ps in sorted(MD.DEEP)] == [9, 9, 10, 10, 10, 11, 11, 11, 11, 12]
+    assert s[129][1] - 64 == s[130][1] - 64 == 1 and s[257][1] - 128 == s[258][1] - 128 == 1      # the last tile's level-1 width: one texel column
+    assert s[260][1] % 2 == 0 and s[260][2] - 64 == 1                   # ... and its level-2 width at 260
+    assert s[513][4] ** 2 > 1024 >= TM.level_sizes(512)[4] ** 2         # 513 is the first platesize at which the tail's loop comes round
+    assert s[721][4] ** 2 >= 2048 > TM.level_sizes(720)[4] ** 2         # 721 the first at which every one of its 1024 threads does
+    assert all(v % 2 == 0 for v in s[1024][:-1]) and s[640][:8] == [640, 320, 160, 80, 40, 20, 10, 5]
+    assert s[1025][4:6] == [65, 33] and len(s[1025]) <= TM.MAX_LEVELS
+
+
+def test_rho_stays_below_2_to_the_23_at_the_largest_platesize():
+    """lod_kernel's `rho << 8` and its comment rest on this bound alone: no GPU test reaches platesizes near it"""
+    ps_max = 26752                                                      # the widest padded plate bk_resize accepts (tests/test_rgba_fb_abi.py)
+    assert (ps_max - 1) * 256 + 255 < 2 ** 23 and ((ps_max - 1) * 256 + 255) << 8 < 2 ** 31
+
+
+@pytest.mark.parametrize("ps,W", [(2, 3), (3, 51), (5, 13), (33, 100), (65, 196)])
+def test_the_ramp_is_the_pixel_loop_and_its_rows_hold_their_step(ps, W):
+    table, sub, (r0, r1) = TM.ramp_case(ps, W, r0=2, H=40)
+    off, tints, W, H, ps = table
+    assert r1 - r0 == len(TM.ramp_steps(ps)) == 3 * (((ps - 1) * 256).bit_length() - 8)
+    o, s = off.reshape(H, W)[r0:r1].reshape(-1), sub.reshape(H, W)[r0:r1].reshape(-1)
+    for bias in (0, -300, 300):
+        np.testing.assert_array_equal(TM.derive_lod(o, s, W, r1 - r0, ps, bias), TM.derive_lod_loops(o, s, W, r1 - r0, ps, bias))
+    _, detail = TM.derive_lod(o, s, W, r1 - r0, ps, detail=True)
+    m = (o != NULL).reshape(r1 - r0, W)
+    for i, step in enumerate(TM.ramp_steps(ps)):
+        assert m[i].any() and (detail["rho"][i][m[i]] == step).all(), (i, step)
+    assert (off.reshape(H, W)[:r0] == NULL).all() and (off.reshape(H, W)[r1:] == NULL).all()
+
+
+def test_census_of_the_deep_ramp():
+    """tests/test_lod_deep_gpu.py's ramp: every targeted rho on a mapped pixel, every lower level below the top at bias 0, the top level at
+    the bias that puts the deepest row on it; steps forward and backward along a row, none and refused ones across rows"""
+    import test_lod_deep_gpu as LD
+    ps, W = LD.RAMP
+    table, sub, (r0, r1) = TM.ramp_case(ps, W)
+    off, tints, W, H, ps = table
+    assert r0 % 8 != 0
+    o, s = off.reshape(H, W)[r0:r1].reshape(-1), sub.reshape(H, W)[r0:r1].reshape(-1)
+    m = o != NULL
+    top = len(TM.level_sizes(ps)) - 1
+    lod, detail = TM.derive_lod(o, s, W, r1 - r0, ps, detail=True)
+    rho = detail["rho"].reshape(-1)[m]
+    targets = [(1 << k) + d for k in range(8, 19) for d in (-1, 0, 1)]      # written out for ps 1025: (ps - 1) * 256 = 2^18
+    assert targets == TM.ramp_steps(ps) and {255, 256, 257, 65535, 65536, 65537, 2 ** 18 + 1} <= set(targets)
+    counts = {t: int((rho == t).sum()) for t in targets}
+    assert all(c > 0 for c in counts.values()), counts
+    assert set(rho.tolist()) == set(targets)                            # ... and nothing else: every step is exact
+    levels = [int(((lod[m] >> 8) == k).sum()) for k in range(top + 1)]
+    assert all(c > 0 for c in levels[:top]) and levels[top] == 0, levels
+    biases = LD.biases(ps)
+    assert biases[:3] == (-300, 0, 300) and biases[3] == 256
+    at_top = TM.derive_lod(o, s, W, r1 - r0, ps, biases[3])[m]
+    assert (at_top == top * 256).sum() == counts[2 ** 18] + counts[2 ** 18 + 1] and at_top.max() == top * 256      # reached, not clamped
+    assert (TM.derive_lod(o, s, W, r1 - r0, ps, 300)[m] == top * 256).sum() > (at_top == top * 256).sum()           # (300 clamps more onto it)
+    assert (TM.derive_lod(o, s, W, r1 - r0, ps, -300)[m] == 0).sum() > (lod[m] == 0).sum()
+    ways = {a: set(detail[a][m.reshape(r1 - r0, W)].tolist()) for a in "hv"}
+    assert ways == dict(h={1, -1}, v={0}) and detail["other_plate"] > 0, ways
+    print(f"ramp ps {ps} W {W} rows {r0}..{r1}: {int(m.sum())} mapped, pixels per rho {min(counts.values())}..{max(counts.values())}, "
+          f"lower level 0..{top} at bias 0: {levels}, on the top level at bias {biases[3]}: {int((at_top == top * 256).sum())}, "
+          f"refused for their plate: {detail['other_plate']} (recorded: 33528 mapped, 1016 a rho, [4064, 3048 nine times, 2032, 0], 2032, 65024)")
+
+
+def right_clamp_reachable(ps, k):
+    """can a position inside a plate of side ps pass the centre of level k's last texel?  The right (bottom) clamp at level k needs
+    U >> k >= (s_k - 1) * 256 + 129 (sx >= 256 with a weight), and U is at most (ps - 1) * 256 + 255.  At ps = 2^n + 1 the last texel of
+    every level k >= 1 holds ONE level-0 column and the answer is no; at ps = 2^n it is yes at every level."""
+    s = TM.level_sizes(ps)[k]
+    return (((s - 1) * 256 + 129) << k) <= (ps - 1) * 256 + 255
+
+
+def test_census_of_the_deep_apply_cases():
+    """tests/test_apply_rgba_fb_trilinear_deep_gpu.py's cases, WITHIN THE OWNED ROWS of each: every level as the lower one; the fractions and
+    tints that matter; a NULL inside a lane beside mapped pixels; and for the rims each of the four clamps at every level k >= 1 with
+    s_k > 1 - the right and the bottom one at every level where a position can reach them at all (right_clamp_reachable).
+    Recorded: the fewest pixels with one lower level 361 (corners 260x257, level 4), 1255 at 1027x1025; a NULL inside a lane 297 to 1742
+    times a case; on the rims the fewest pixels at one clamp and level: left / top 223 (260x257, level 4), right / bottom 826 at 1026x1024
+    (every level 1 to 10) and 558 at 724x721 (levels 5, 7, 8; 0 at 1, 2, 3, 4, 6, 9 and at every level of 257, 513, 1025, as the geometry says)"""
+    import test_apply_rgba_fb_trilinear_deep_gpu as TD
+    assert [right_clamp_reachable(1024, k) for k in range(1, 10)] == [True] * 9
+    assert not any(right_clamp_reachable(ps, k) for ps in (257, 513, 1025) for k in range(1, len(TM.level_sizes(ps)) - 1))
+    assert [k for k in range(1, 10) if right_clamp_reachable(721, k)] == [5, 7, 8]
+    sides = ("left", "right", "top", "bottom")
+    for name, kind, (off, tints, W, H, ps), sub, lod, (r0, r1) in TD.deep_cases():
+        assert ps == min(W, H) == H and r0 % 8 != 0 and 0 < r0 < r1 < H and 16 <= r1 - r0 <= 18
+        own = lambda a: np.asarray(a).reshape(H, W)[r0:r1]
+        off, sub, tints, lod = own(off), own(sub), own(tints), own(lod)
+        sizes = TM.level_sizes(ps)
+        top = len(sizes) - 1
+        assert top >= 9 and (lod <= top * 256).all()
+        m = off != NULL
+        mapped, plate, U, V = TM.positions(off[m], sub[m], ps)
+        lo, fl = lod[m].astype(np.int64) >> 8, lod[m] & 255
+        lower = [int((lo == k).sum()) for k in range(top + 1)]
+        assert min(lower) >= 200, (name, lower)                         # (the smallest stripe: 17 x 260 pixels, a fifth of them NULL, over 10 levels)
+        assert {0, 1, 127, 128, 255} <= set(fl.tolist()), name
+        assert {0, 1, 2, 3, 4, 5, 6, 200, 255} <= set(tints[m].tolist()), name
+        lanes = m[:, :W - W % 4].reshape(r1 - r0, -1, 4).sum(axis=2)
+        null_in_lane = int(((lanes > 0) & (lanes < 4)).sum())
+        assert null_in_lane > 0, name
+        clamped = {side: [0] * (top + 1) for side in sides}
+        for k in range(1, top + 1):
+            at = (lo == k) | (np.minimum(lo + 1, top) == k)
+            Uk, Vk, s = U[at] >> k, V[at] >> k, sizes[k]
+            sx, sy = (Uk & 255) + 128, (Vk & 255) + 128
+            clamped["left"][k] = int((((Uk >> 8) == 0) & (sx < 256)).sum())
+            clamped["right"][k] = int((((Uk >> 8) == s - 1) & (sx >= 256) & ((sx & 255) > 0)).sum())
+            clamped["top"][k] = int((((Vk >> 8) == 0) & (sy < 256)).sum())
+            clamped["bottom"][k] = int((((Vk >> 8) == s - 1) & (sy >= 256) & ((sy & 255) > 0)).sum())
+        if kind == "corners":
+            for k in range(1, top + 1):
+                if sizes[k] > 1:
+                    for side in sides:
+                        if side in ("left", "top") or right_clamp_reachable(ps, k):
+                            assert clamped[side][k] > 0, (name, side, k, clamped)
+                        else:
+                            assert clamped[side][k] == 0, (name, side, k)
+        print(f"{name} rows {r0}..{r1}: {int(m.sum())} mapped, lower level 0..{top}: {lower}, NULL inside a lane {null_in_lane}, clamps per level 1..{top} "
+              + ", ".join(f"{side} {clamped[side][1:]}" for side in sides))

@@ -2,7 +2,7 @@
 
 1. pyramid: the mip levels of a plate ((a + b + c + d + 2) >> 2 over clamped coordinates, each level from the rounded one below).
 2. derive_lod: the level-of-detail plane from a reference-layout table and its sub-texel plane (neighbour differences, the
-   piecewise-linear log2, bias, clamp).
+   piecewise-linear log2, bias, clamp); ramp_case: a directed table that places chosen values of rho.
 3. trilinear_frame: what the call writes.  Every level's four texels and weights come from subtexel_model.neighbours - the bilinear
    stage itself - handed (Uk >> 8, Uk & 255) in the place of (px, qx) and s_k in the place of ps.
 Each has a second formulation in plain Python loops (*_loops) that tests/test_trilinear_cpu.py holds it to."""
@@ -85,7 +85,8 @@ def positions(off, sub, ps):
 
 def derive_lod(off, sub, W, rows, ps, bias=0, detail=False):
     """off (reference layout), sub: the OWNED rows, [rows * W] -> uint16 [rows * W]; detail: also dict(h=, v=) of int8 [rows][W]:
-    1 = the step went forward, -1 = backward, 0 = none (unmapped pixels 0), and other_plate = mapped neighbours refused for their plate"""
+    1 = the step went forward, -1 = backward, 0 = none (unmapped pixels 0), other_plate = mapped neighbours refused for their plate, and
+    rho = int64 [rows][W], the larger of the two steps in 1/256 texel (what lod_value is given; meaningless where unmapped)"""
     m, plate, U, V = (a.reshape(rows, W) for a in positions(off, sub, ps))
     steps, way, refused = [], {}, 0
     for axis, name in ((1, "h"), (0, "v")):
@@ -106,7 +107,7 @@ def derive_lod(off, sub, W, rows, ps, bias=0, detail=False):
         way[name] = np.where(okf, 1, np.where(okb, -1, 0)).astype(np.int8)
     rho = np.maximum(steps[0], steps[1])
     lod = np.where(m, lod_value(rho, bias, len(level_sizes(ps))), 0).astype(np.uint16).reshape(-1)
-    return (lod, dict(way, other_plate=refused)) if detail else lod
+    return (lod, dict(way, other_plate=refused, rho=rho)) if detail else lod
 
 
 def derive_lod_loops(off, sub, W, rows, ps, bias=0):
@@ -136,6 +137,40 @@ def derive_lod_loops(off, sub, W, rows, ps, bias=0):
                             break
             out[y * W + x] = lod_value_loops(rho, bias, levels)
     return out
+
+
+def ramp_steps(ps):
+    """the values of rho a ramp table places on purpose: 2^k - 1, 2^k, 2^k + 1 for k = 8 (the rho <= 256 edge: 255, 256, 257) up to
+    floor(log2((ps - 1) * 256)), the largest power of two a step inside one plate can reach; ps >= 2"""
+    kmax = ((ps - 1) * 256).bit_length() - 1
+    return [(1 << k) + d for k in range(8, kmax + 1) for d in (-1, 0, 1)]
+
+
+def ramp_case(ps, W, r0=3, H=None):
+    """((off, tints, W, H, ps), sub, (r0, r1)), H = ps unless given (a model may be handed any H): a DIRECTED table for the level of detail.  One row per value of ramp_steps(ps), from
+    row r0 on, everything else NULL.  Row i lies on plate i % 6 at one V, so both vertical neighbours are refused for their plate and the
+    vertical step is 0; along the row U starts below 255 and advances by the row's step, turning round where it would leave
+    [0, (ps - 1) * 256 + 255], so |dU| is the step at every pixel; a NULL every 97 pixels sends its left neighbour to the backward step.
+    rho is therefore the row's step at every mapped pixel of it (W >= 3)."""
+    steps = ramp_steps(ps)
+    H, umax = H or ps, (ps - 1) * 256 + 255
+    assert W >= 3 and ps >= 2 and r0 + len(steps) <= H
+    off = np.full((H, W), NULL, np.uint32)
+    sub = np.full((H, W), SM.CENTRE, np.uint16)
+    for i, step in enumerate(steps):
+        u, way, us = (37 * i + 11) % 255, 1, []
+        for _ in range(W):
+            us.append(u)
+            if not 0 <= u + way * step <= umax:
+                way = -way
+            u += way * step
+            assert 0 <= u <= umax
+        U, V = np.array(us, np.int64), ((5 * i + 1) % ps) * 256 + (29 * i) % 256
+        off[r0 + i] = (i % 6) * ps * ps + (V >> 8) * ps + (U >> 8)
+        sub[r0 + i] = (U & 255) | ((V & 255) << 8)
+        off[r0 + i, 50::97] = NULL
+    tints = np.full(H * W, 255, np.uint8)
+    return (off.reshape(-1), tints, W, H, ps), sub.reshape(-1), (r0, r0 + len(steps))
 
 
 # ---- 3. the frame ---------------------------------------------------------------------------------------------------------------------
